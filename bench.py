@@ -13,7 +13,9 @@ scaling of a single instance; barrier + max-over-ranks timing.  The instance-lev
 (each rank its own instance, dataset/run_lorads.sh:85-114, weak scaling, no data-path
 collective) are reported beside it under `replicas`.
 
-Prints one JSON line (rank 0).  Besides the contract keys:
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes the
+timed solve's final state with --dump-outputs DIR and prints the contract keys (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...).  With --full, besides the contract keys:
   roofline          dominant split-iteration stage on the workload (HIP-event timed,
                     algorithmic bytes from lrs_stage_bytes; DESIGN.md "Kernels")
   roofline_at_scale the same stages on a 2000 x 2000 torus (n = 4e6, r = 16: factors
@@ -116,6 +118,23 @@ def attach_traffic(res, leg):
     res["traffic_source"] = (f"{prof['_source']}: per launch, rocprofv3 FETCH_SIZE x2 + WRITE_SIZE summed over the "
                              "stage's kernels, full relaunches only (scripts/leg_profile.sh)")
     return res
+
+
+def instance_cache():
+    """Directory of the generated instance files: .bench_instances in the tree, or, where the tree
+    cannot be written (a read-only checkout, another user's), a per-user directory under the
+    system's temporary directory -- the same path on every rank."""
+    import tempfile
+    cache = os.path.join(ROOT, ".bench_instances")
+    try:
+        os.makedirs(cache, exist_ok=True)
+        if os.access(cache, os.W_OK | os.X_OK):
+            return cache
+    except OSError:
+        pass
+    cache = os.path.join(tempfile.gettempdir(), f"lrsdp_bench_instances_{os.getuid()}")
+    os.makedirs(cache, exist_ok=True)
+    return cache
 
 
 def instance_for(rank_id, rows, cols, cache, seed0=67):
@@ -423,6 +442,36 @@ def sharded_strong(solver, dist, world, rank_id, local, cache, replicas, steps=5
     return res
 
 
+DUMP_CAP_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(sv, out_dir):
+    """--dump-outputs: what the timed solve leaves its caller after its last inner iteration, as
+    float64 <name>.npy under `out_dir`: the factor R, the gradient G, lambda, A(RR^T), the newest
+    L-BFGS pair (s, y) and the last trip's (tau, ||G||^2, pinf, beta) -- the state alm_steps
+    returns.  The instance and the initial point are seeded, so two builds run with the same
+    arguments start from identical inputs.  An array over its share of DUMP_CAP_BYTES is stored
+    as a fixed seeded sample of its entries (ascending indices, the same for every run)."""
+    import ctypes as C
+
+    import numpy as np
+    solver = importlib.import_module(PKG + ".solver")
+    last = (C.c_double * 4)()
+    newest = C.c_int()
+    sv._check(sv.lib.lrs_alm_last_step(sv.ctx, last, C.byref(newest)), "alm_last_step")
+    pair = (solver.S0, solver.Y0) if newest.value == 0 else (solver.S1, solver.Y1)
+    arrays = {"R": sv.get_factor(solver.R), "G": sv.get_factor(solver.G), "lambda": sv.get_vec(solver.LAMBDA),
+              "cvs": sv.get_vec(solver.CVS), "s": sv.get_factor(pair[0]), "y": sv.get_factor(pair[1]),
+              "last_step": np.array(list(last), dtype=np.float64)}
+    cap = (DUMP_CAP_BYTES - 4096 * len(arrays)) // len(arrays) // 8   # entries per file, headers left out
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(20).choice(a.size, size=cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def build_provenance():
     """sha256 (first 16 hex) of the HIP library this run loads and of the sources it is built
     from, and the library's mtime: whether the box ran the build of these sources is checkable
@@ -540,6 +589,8 @@ def sharded_headline_line(args, world, rank_id, dist, replicas, solver, local, c
         clock["t1"] = time.perf_counter()
 
     out = sv.alm_timed(max(1, args.warmup), args.steps, on_start, on_stop, fixedRank=r, reoptLevel=0)
+    if args.dump_outputs and rank_id == 0:
+        dump_outputs(sv, args.dump_outputs)   # rank 0's shard: its owned + halo rows, its constraints
     sv.close()
     _, t_max = replicas.aggregate(dist, 0, clock["t1"] - clock["t0"])
     return r, out["done"] / t_max, out["done"], t_max, info
@@ -597,6 +648,13 @@ def main():
                          "the sharded iteration over a one-rank RCCL communicator)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch + barrier/aggregate protocol only over gloo, no GPU (CPU tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also every other leg (roofline, wall clock to eps, CPU baseline, "
+                         "north star, configs, at scale, C5, C5b, sharded; each can be dropped with its --no-*); "
+                         "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the state the timed solve ends with (R, G, lambda, A(RR^T), "
+                         "the newest L-BFGS pair, the last trip's scalars) as DIR/<name>.npy")
     args = ap.parse_args()
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -627,8 +685,7 @@ def main():
         return
 
     solver = importlib.import_module(PKG + ".solver")
-    cache = os.path.join(ROOT, ".bench_instances")
-    os.makedirs(cache, exist_ok=True)
+    cache = instance_cache()
     failed = 0
     sharded_head = None
     if world > 1:
@@ -674,6 +731,10 @@ def main():
     out = sv.alm_timed(max(1, args.warmup), args.steps, on_start, on_stop, **kw)
     dt = clock["t1"] - clock["t0"]
     done = out["done"]
+    if done != args.steps:
+        raise RuntimeError(f"timed {done} inner iterations, --steps asked for {args.steps}")
+    if args.dump_outputs and rank_id == 0 and world == 1:
+        dump_outputs(sv, args.dump_outputs)
     done_tot, t_max = replicas.aggregate(dist, done, dt)
 
     line = {
@@ -696,8 +757,9 @@ def main():
         "headline": headline_kind(world),
         "alm_phase_rate": done / out["seconds"],
         "build": build_provenance(),
-        "roofline": stage_roofline(sv, 300, leg="g67"),
     }
+    if args.full:
+        line["roofline"] = stage_roofline(sv, 300, leg="g67")
     if world > 1:
         # value = the single row-sharded instance; the per-rank instances (this run's unsharded
         # solves above) are the weak-scaling replicas
@@ -718,7 +780,7 @@ def main():
             line["config"]["parallelism"] = f"replicas x{world} (instance-level, weak) -- sharded headline FAILED"
             line["headline"] = "replicas (the sharded headline FAILED: see sharded_headline.error)"
             line["sharded_headline"] = sharded_head
-    if rank_id == 0 and world == 1 and not args.no_eps:
+    if args.full and rank_id == 0 and world == 1 and not args.no_eps:
         eps_flags = dict(reoptLevel=0, heuristicFactor=10.0, phase1Tol=1e-2, phase2Tol=1e-5)
         t1 = time.perf_counter()
         sol = sv.solve(**eps_flags)
@@ -729,7 +791,7 @@ def main():
                                      "primal_obj": sol["pobj"], "alm_primal_obj": sol["alm_pobj"],
                                      "pinf": sol["pinf"], "gap": sol["gap"], "rank": sol["final_rank"]}
     sv.close()
-    if rank_id == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank_id == 0 and world == 1 and not args.no_cpu:
         it, sec, kind = cpu_reference_rate(path, r, args.cpu_seconds)
         nthr, model = host_cpu()
         line["cpu_baseline"] = {"value": it / sec, "unit": "ALM inner iterations/s", "cores": 1, "kind": kind,
@@ -750,7 +812,7 @@ def main():
                                       timeout=600)
             if ref:
                 line["cpu_baseline"]["wall_clock_to_eps"] = ref
-    if rank_id == 0 and world == 1 and not args.no_north_star:
+    if args.full and rank_id == 0 and world == 1 and not args.no_north_star:
         # BASELINE.json target: >= 10x CPU LoRADS it/s on MaxCut n = 20 000, rank 64, 1 GPU
         p81 = instance_for(0, 100, 200, cache, seed0=81)
         s81 = solver.Solver(p81, device=local)
@@ -766,7 +828,7 @@ def main():
             ns["cpu_kind"] = kind
             ns["speedup"] = ns["gpu_it_s"] / ns["cpu_it_s"]
         line["north_star"] = ns
-    if rank_id == 0 and world == 1 and not args.no_configs:
+    if args.full and rank_id == 0 and world == 1 and not args.no_configs:
         # the other BASELINE.json configs as whole solves to eps = 1e-5 with benchmark.py's
         # flags for their subtype (get_lorads_params, benchmark.py:136-200), device vs reference
         inst = importlib.import_module(PKG + ".instances")
@@ -790,7 +852,7 @@ def main():
                     row["speedup"] = ref["solve_time_sec"] / res["solve_time"]
             rows.append(row)
         line["configs_wall_clock_to_eps"] = rows
-    if rank_id == 0 and world == 1 and not args.no_scale:
+    if args.full and rank_id == 0 and world == 1 and not args.no_scale:
         # roofline at scale: 2000 x 2000 torus built in memory (lrs_load_coo), rank 16
         inst = importlib.import_module(PKG + ".instances")
         t1 = time.perf_counter()
@@ -804,11 +866,11 @@ def main():
         rl["load_sec"] = load_s
         big.close()
         line["roofline_at_scale"] = rl
-    if rank_id == 0 and world == 1 and not args.no_c5:
+    if args.full and rank_id == 0 and world == 1 and not args.no_c5:
         line["config_c5"] = config_c5(solver, local, cpu_seconds=0.0 if args.no_cpu else 20.0, cache=cache)
-    if rank_id == 0 and world == 1 and not args.no_c5b:
+    if args.full and rank_id == 0 and world == 1 and not args.no_c5b:
         line["config_c5b"] = config_c5b(solver, local, ref_densec=ref_densec_rates())
-    if not args.no_sharded:
+    if args.full and not args.no_sharded:
         # a watchdog keeps a stuck collective from swallowing the result line
         import threading
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU-box jobs of this round, one argument each (run through gpurun from the repo root):
 #   tests [pytest args]  the -m gpu suite (or the named tests), one process, per-test timeout
-#   bench [bench args]   one bench.py line
+#   bench [bench args]   one bench.py line (pass --full for every leg, not the headline alone)
 #   c5probe              C5 kernel table (scripts/c5_probe.py)
 # Every GPU step has its own time limit; the first failure ends the job.
 set -o pipefail
