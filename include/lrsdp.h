@@ -259,6 +259,23 @@ int lrs_mfma_f64_probe(lrs_ctx *ctx, int waves_per_simd, int chains, double *tfl
  * (k_cgemm, 2 n^2 r flop), averaged over `reps`.  Fails when the cone has no dense objective. */
 int lrs_time_dense(lrs_ctx *ctx, int cone, int reps, double *avg_ms);
 
+/* Dense constraint matrices (the reference's SDP_COEFF_DENSE, data/lorads_sdp_data.c:1187-1191:
+ * an A_i with more than 10 % of the cone's lower triangle, strictly).  A cone on the dense-A
+ * path (LRS_DENSE_A=1; unset: at least 320 000 entries in the cone's dense A_i; LRS_DENSE_A=0: never) keeps those A_i out of the slot
+ * pattern as a stack of full n x n matrices and evaluates them on the FP64 matrix cores
+ * (k_dcon_ax); its ALM inner loop is the operator-composed one.  Sharded
+ * contexts refuse such a problem.
+ * lrs_dense_a_info: the cone's number of dense coefficients (whichever path), whether it took
+ * the dense path at load, and the stack's bytes (0 off the path); outputs may be NULL.
+ * lrs_time_dense_a: ms per k_dcon_ax launch over the cone's whole stack on R (A_i R and the
+ * dots <R, A_i R>), averaged over `reps` back-to-back launches; fails when the cone is not on
+ * the dense path.
+ * lrs_dense_a_plan: host-only (no device, no context) classification of the instance at `path`:
+ * cons (may be NULL) receives up to cap 0-based constraint indices of the cone's dense A_i. */
+int lrs_dense_a_info(lrs_ctx *ctx, int cone, int *n_dense, int *on_dense_path, long *stack_bytes);
+int lrs_time_dense_a(lrs_ctx *ctx, int cone, int reps, double *avg_ms);
+int lrs_dense_a_plan(const char *path, int cone, int *n_dense, int *on_dense_path, int *cons, int cap);
+
 /* Per-stage timing of the split ALM inner iteration: runs `steps` inner iterations at
  * the current rank like lrs_alm_throughput, with HIP events on the solver stream
  * around each of the four launches (S1 direction+SDDMM, S2 q-gather, S3 update+

@@ -119,6 +119,13 @@ struct DevCone {
     int dense_c = 0;
     double *Cd = nullptr;
     double c_alpha = 0.0;
+    // dense constraint coefficients (lrs_problem.h HostCone::dA), not in the slots: kd full
+    // n x n row-major symmetric matrices, coefficient j at dA + j n^2, of constraint dA_con[j]
+    int kd = 0;
+    double *dA = nullptr;
+    int *dA_con = nullptr;
+    std::vector<int> dA_con_h;
+    const double *dSd = nullptr;         // while the dual infeasibility runs: S_d = -sum_j lambda_j A_j (n x n)
     // long rows (>= kTileMinDeg adjacency entries per row on average): per row, the first entry
     // at or past column x n / kNX, x = 0..kNX ([n][kNX + 1]); the column-tiled k_wide_* kernels
     int *colseg = nullptr;
@@ -245,6 +252,7 @@ struct DevProblem {
     double *spack = nullptr;                                 // [nsh] one m-vector's shared entries
     std::vector<DevCone> cones;
     int ndense = 0;                                          // cones with a dense objective (DevCone::Cd)
+    int ndensea = 0;                                         // cones on the dense-A path (DevCone::dA)
     bool tiles = false;                                      // column-tiled long-row kernels (LRS_TILES=1 at alloc)
     double *gp = nullptr;                                    // DevWork::GP (kNX partial factors), the tiled S X's scratch
     double *cgk = nullptr;                                   // DevWork::CGK: k_cgemm2's split-K slabs (kCgSplitSlabs x NRpad)
@@ -264,6 +272,9 @@ struct DevWork {
     // through the inner loop, recomputed by op_grad) and C D of the iteration; zero elsewhere
     double *CR = nullptr, *CD = nullptr;
     double *CGK = nullptr;   // k_cgemm2's split-K slabs (dense cones of >= 2048 rows): kCgSplitSlabs x NR
+    // dense-A cones (DevCone::dA), sized for the largest: dT the products T_i = A_i X (kd x n x ld),
+    // dSd one full matrix sum_i w_i A_i (n x n), dpart k_dcon_ax's tile partials
+    double *dT = nullptr, *dSd = nullptr, *dpart = nullptr;
     // column-tiled long-row kernels: kNX partial S R_new factors (kNX * NRpad), null when no cone
     // has long rows
     double *GP = nullptr;
@@ -344,6 +355,26 @@ int launch_dense_cx(const DevProblem &P, int cone, const double *X, double *Y, d
 // ALM iteration, between stage A and B: CD = scale C D of every dense cone, and the partials
 // <R, CD>, <D, CD> (slots 0, 1 of 8) of stage A's objective terms at partial offset `off`
 // (R: the current iterate by the control block); returns the partial blocks written
+// dense constraint coefficients of cone `cone` (DevCone::dA, kd matrices; lrs_kernels.hip
+// "dense constraint coefficients").  launch_dcon_ax: T_i = A_i X for the nmat matrices at A
+// (the cone's stack, or one n x n matrix), X / Z full factor buffers; the tiles' partial dots
+// <X, T_i>, <Z, T_i> into dpart (2 nmat dcon_tiles doubles); T (optional) cone-local, matrix i
+// at T + i n ld.  launch_dcon_fin: the partials per matrix in tile order, out0[con_i] (+)= s0
+// <X, T_i>, out1[con_i] (+)= s1 <Z, T_i>, out1b[con_i] += s1 <Z, T_i> (each optional).
+int dcon_tiles(const DevCone &c);
+int launch_dcon_ax(const DevProblem &P, int cone, int nmat, const double *A, const double *X, const double *Z,
+                   double *T, double *dpart, hipStream_t st);
+int launch_dcon_fin(const DevProblem &P, int cone, const double *dpart, double s0, double *out0, double s1,
+                    double *out1, double *out1b, int accumulate, hipStream_t st);
+// Sd (n x n) = sum_i w[con_i] A_i, i ascending
+int launch_dcon_wsum(const DevProblem &P, int cone, const double *w, double *Sd, hipStream_t st);
+// out rows of the cone = beta out + scale sum_i w[con_i] T_i (out, dotx full factor buffers);
+// with dotx and part: the blocks' partial <dotx, out> in part[0 .. *nblk)
+int launch_dcon_comb(const DevProblem &P, int cone, const double *w, const double *T, double scale, double beta,
+                     double *out, const double *dotx, double *part, int *nblk, hipStream_t st);
+// out[con_i] (+)= <p, T_i>, outb[con_i] += it (optional)
+int launch_dcon_dots(const DevProblem &P, int cone, const double *T, const double *p, double *out, double *outb,
+                     int accumulate, hipStream_t st);
 int dense_cd_blocks(const DevProblem &P);
 int launch_dense_cd(const DevProblem &P, const DevWork &W, const double *ctrl, int off, hipStream_t st);
 

@@ -1195,6 +1195,22 @@ __global__ void __launch_bounds__(kBlock) k_alm_gather_q(int m, int K, const int
     partials_finalize<5>(acc, part, ticket, fin);
 }
 
+// the same five reductions from complete q1, q2 (a problem with a cone on the dense-A path:
+// op_q12_fin has added the dense coefficients' values, which no slot gather sees)
+__global__ void __launch_bounds__(kBlock) k_ls_red_q(int m, const double *__restrict__ b, const double *__restrict__ cvs,
+                                                     const double *__restrict__ lam, const double *__restrict__ par,
+                                                     const double *__restrict__ q1, const double *__restrict__ q2,
+                                                     double *part, unsigned *ticket, double *fin) {
+    const double rhoInv = 1.0 / par[P_RHO];
+    double acc[5] = {0, 0, 0, 0, 0};
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < m; i += gridDim.x * kBlock) {
+        const double v1 = q1[i], v2 = q2[i];
+        const double q0 = (b[i] - cvs[i]) + rhoInv * lam[i];
+        acc[0] += v2 * v2; acc[1] += v1 * v2; acc[2] += q0 * v2; acc[3] += v1 * v1; acc[4] += q0 * v1;
+    }
+    partials_finalize<5>(acc, part, ticket, fin);
+}
+
 // LORADScubic_equation (lorads_alm.c:191-231)
 __device__ int dev_cubic(double a, double b, double c, double d, double *res) {
     const double A = b * b - 3 * a * c, B = b * c - 9 * a * d, C = c * c - 3 * b * d;
@@ -4357,6 +4373,15 @@ int launch_trl_symv(const DevProblem &P, int cone, const double *S, const double
         }
         LRS_CHECK_LAUNCH();
     }
+    if (c.dSd) {   // dense-A cone: y += S_d v, S_d = sum_i w_i A_i as one full matrix (launch_dcon_wsum)
+        if (!vj && b2) {
+            snprintf(g_err, sizeof(g_err), "trl: dense-A cone needs the normalized vector");
+            return -1;
+        }
+        const int grid = std::max(1, std::min(2048, (c.n + kBlock / 64 - 1) / (kBlock / 64)));
+        hipLaunchKernelGGL(k_trl_dense, dim3(grid), dim3(kBlock), 0, st, c.n, c.n, 0, 1.0, c.dSd, vj ? vj : x, y);
+        LRS_CHECK_LAUNCH();
+    }
     return 0;
 }
 
@@ -5451,6 +5476,205 @@ int launch_dense_cd(const DevProblem &P, const DevWork &W, const double *ctrl, i
         }
         LRS_CHECK_LAUNCH();
     }
+    return 0;
+}
+
+// ---- dense constraint coefficients on the FP64 matrix cores.  The reference
+// evaluates an SDP_COEFF_DENSE A_i with its own BLAS branches (denseAUV, dataMatDenseMultiRkMat,
+// data/lorads_sdp_data.c:843-856, :948-973); here the cone's dense A_i form a stack of full
+// n x n row-major matrices (DevCone::dA) and every term is a product with it:
+// <A_i, sym(X Z^T)> = <Z, A_i X>, A^*(w) X = sum_i w_i (A_i X).
+// k_dcon_ax: T_i = A_i X for every matrix i of the stack, X row-major n x ld.  One block per
+// (i, output tile of kCgBM rows x kCgBN columns); the tile loop is k_cgemm's (four waves as
+// 2 x 2, a wave 16 rows x 32 columns, double-buffered LDS tiles of kCgBK k-rows).  Epilogue:
+// the block's partial dots <X, T_i> and <Z, T_i> over its tile into dpart[2 blockIdx.x + {0, 1}]
+// (Z may be null: 0), which k_dcon_fin adds per i in tile order -- no atomics, bitwise
+// reproducible.  T (may be null) receives the products, matrix i at T + i n ld.
+__global__ void __launch_bounds__(kBlock) k_dcon_ax(int n, int r, int ld, int ntn, int ntile,
+                                                    const double *__restrict__ A, const double *__restrict__ X,
+                                                    const double *__restrict__ Z, double *__restrict__ T,
+                                                    double *__restrict__ dpart) {
+    __shared__ double Cs[2][kCgBM][kCgBK + 1];
+    __shared__ double Xs[2][kCgBK][kCgBN + 1];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wm = w >> 1, wn = w & 1;
+    const int mat = blockIdx.x / ntile, tile = blockIdx.x % ntile;
+    const double *__restrict__ Ai = A + (long)mat * n * n;
+    const int nk = (n + kCgBK - 1) / kCgBK;
+    const int crow = threadIdx.x >> 3, ck = (threadIdx.x & 7) * 4;
+    const int xrow = threadIdx.x >> 3, xc = (threadIdx.x & 7) * 8;
+    const int m0 = (tile / ntn) * kCgBM, n0 = (tile % ntn) * kCgBN;
+    gram_acc_t acc[2] = {gram_acc_t{0.0, 0.0, 0.0, 0.0}, gram_acc_t{0.0, 0.0, 0.0, 0.0}};
+    double cr[4], xr[8];
+    auto gload = [&](int k0) {
+        const int gi = m0 + crow;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int gk = k0 + ck + t;
+            cr[t] = (gi < n && gk < n) ? Ai[(long)gi * n + gk] : 0.0;
+        }
+        const int gk = k0 + xrow;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const int col = n0 + xc + t;
+            xr[t] = (gk < n && col < r) ? X[(long)gk * ld + col] : 0.0;
+        }
+    };
+    auto sstore = [&](int buf) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) Cs[buf][crow][ck + t] = cr[t];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) Xs[buf][xrow][xc + t] = xr[t];
+    };
+    gload(0);
+    sstore(0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const int cur = kt & 1;
+        if (kt + 1 < nk) gload((kt + 1) * kCgBK);
+#pragma unroll
+        for (int ks = 0; ks < kCgBK / 4; ++ks) {
+            const double a = Cs[cur][wm * 16 + (lane & 15)][ks * 4 + (lane >> 4)];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const double b = Xs[cur][ks * 4 + (lane >> 4)][wn * 32 + t * 16 + (lane & 15)];
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
+            }
+        }
+        if (kt + 1 < nk) sstore(cur ^ 1);
+        __syncthreads();
+    }
+    // D fragment: col = lane & 15, row = (lane >> 4) + 4 q
+    double dots[2] = {0.0, 0.0};
+    double *__restrict__ Ti = T ? T + (long)mat * n * ld : nullptr;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = m0 + wm * 16 + (lane >> 4) + 4 * q;
+            const int col = n0 + wn * 32 + t * 16 + (lane & 15);
+            if (row < n && col < r) {
+                const long o = (long)row * ld + col;
+                const double v = acc[t][q];
+                if (Ti) Ti[o] = v;
+                dots[0] += X[o] * v;
+                if (Z) dots[1] += Z[o] * v;
+            }
+        }
+    double s[2];
+    block_reduce<2>(dots, s);
+    if (threadIdx.x == 0) {
+        dpart[2 * (long)blockIdx.x] = s[0];
+        dpart[2 * (long)blockIdx.x + 1] = s[1];
+    }
+}
+// the tiles' partial dots of k_dcon_ax, per matrix j in tile order: v0 = sum <X, T_j>, v1 =
+// sum <Z, T_j>; out0[con_j] (+)= s0 v0 when out0, out1[con_j] (+)= s1 v1 when out1, and
+// out1b[con_j] += s1 v1 when out1b (a second accumulator of the same value: the per-cone
+// constraint values next to their sum).  A thread a matrix.
+__global__ void __launch_bounds__(kBlock) k_dcon_fin(int kd, int ntile, const int *__restrict__ con,
+                                                     const double *__restrict__ dpart, double s0, double *out0,
+                                                     double s1, double *out1, double *out1b, int accumulate) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= kd) return;
+    double v0 = 0.0, v1 = 0.0;
+    for (int t = 0; t < ntile; ++t) {
+        v0 += dpart[2 * ((long)j * ntile + t)];
+        v1 += dpart[2 * ((long)j * ntile + t) + 1];
+    }
+    const int i = con[j];
+    if (out0) out0[i] = (accumulate ? out0[i] : 0.0) + s0 * v0;
+    if (out1) out1[i] = (accumulate ? out1[i] : 0.0) + s1 * v1;
+    if (out1b) out1b[i] += s1 * v1;
+}
+// S_d = sum_j w[con_j] A_j over the stack, j ascending per element (the full-matrix form of the
+// adjoint: the dual infeasibility's Lanczos multiplies one fixed S hundreds of times)
+__global__ void __launch_bounds__(kBlock) k_dcon_wsum(long nn, int kd, const int *__restrict__ con,
+                                                      const double *__restrict__ w, const double *__restrict__ A,
+                                                      double *__restrict__ Sd) {
+    for (long e = (long)blockIdx.x * kBlock + threadIdx.x; e < nn; e += (long)gridDim.x * kBlock) {
+        double t = 0.0;
+        for (int j = 0; j < kd; ++j) t += w[con[j]] * A[(long)j * nn + e];
+        Sd[e] = t;
+    }
+}
+// k_dcon_comb: the adjoint's combination out = beta out + scale sum_j w[con_j] T_j on the cone's
+// n x ld rows (columns < r), j ascending; with dotx, the block's partial <dotx, out> into
+// part[blockIdx.x] (the CG's fused <p, Q>, launch_cg_mv's layout)
+__global__ void __launch_bounds__(kBlock) k_dcon_comb(int n, int r, int ld, int kd, const int *__restrict__ con,
+                                                      const double *__restrict__ w, const double *__restrict__ T,
+                                                      double scale, double beta, double *__restrict__ out,
+                                                      const double *__restrict__ dotx, double *__restrict__ part) {
+    const long tot = (long)n * ld;
+    double acc[1] = {0.0};
+    for (long e = (long)blockIdx.x * kBlock + threadIdx.x; e < tot; e += (long)gridDim.x * kBlock) {
+        if ((int)(e % ld) >= r) continue;
+        double t = 0.0;
+        for (int j = 0; j < kd; ++j) t += w[con[j]] * T[(long)j * tot + e];
+        const double v = (beta != 0.0 ? beta * out[e] : 0.0) + scale * t;
+        out[e] = v;
+        if (dotx) acc[0] += dotx[e] * v;
+    }
+    if (part) write_partials<1>(acc, part, blockIdx.x);
+}
+// <p, T_j> per matrix j (a block a matrix, fixed order): out[con_j] (+)= the value, and
+// outb[con_j] += it when outb
+__global__ void __launch_bounds__(kBlock) k_dcon_dots(int n, int r, int ld, const int *__restrict__ con,
+                                                      const double *__restrict__ T, const double *__restrict__ p,
+                                                      double *out, double *outb, int accumulate) {
+    const long tot = (long)n * ld;
+    const double *__restrict__ Tj = T + (long)blockIdx.x * tot;
+    double acc[1] = {0.0};
+    for (long e = threadIdx.x; e < tot; e += kBlock)
+        if ((int)(e % ld) < r) acc[0] += p[e] * Tj[e];
+    double s[1];
+    block_reduce<1>(acc, s);
+    if (threadIdx.x == 0) {
+        const int i = con[blockIdx.x];
+        out[i] = (accumulate ? out[i] : 0.0) + s[0];
+        if (outb) outb[i] += s[0];
+    }
+}
+int dcon_tiles(const DevCone &c) { return ((c.n + kCgBM - 1) / kCgBM) * ((c.r + kCgBN - 1) / kCgBN); }
+int launch_dcon_ax(const DevProblem &P, int cone, int nmat, const double *A, const double *X, const double *Z,
+                   double *T, double *dpart, hipStream_t st) {
+    const DevCone &c = P.cones[cone];
+    const int ntile = dcon_tiles(c);
+    hipLaunchKernelGGL(k_dcon_ax, dim3(nmat * ntile), dim3(kBlock), 0, st, c.n, c.r, c.ld, (c.r + kCgBN - 1) / kCgBN,
+                       ntile, A, X + c.foff, Z ? Z + c.foff : nullptr, T, dpart);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_dcon_fin(const DevProblem &P, int cone, const double *dpart, double s0, double *out0, double s1,
+                    double *out1, double *out1b, int accumulate, hipStream_t st) {
+    const DevCone &c = P.cones[cone];
+    hipLaunchKernelGGL(k_dcon_fin, dim3(grid_elems(c.kd, 1)), dim3(kBlock), 0, st, c.kd, dcon_tiles(c), c.dA_con, dpart,
+                       s0, out0, s1, out1, out1b, accumulate);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_dcon_wsum(const DevProblem &P, int cone, const double *w, double *Sd, hipStream_t st) {
+    const DevCone &c = P.cones[cone];
+    const long nn = (long)c.n * c.n;
+    hipLaunchKernelGGL(k_dcon_wsum, dim3(grid_elems(nn, 1)), dim3(kBlock), 0, st, nn, c.kd, c.dA_con, w, c.dA, Sd);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_dcon_comb(const DevProblem &P, int cone, const double *w, const double *T, double scale, double beta,
+                     double *out, const double *dotx, double *part, int *nblk, hipStream_t st) {
+    const DevCone &c = P.cones[cone];
+    const int grid = std::min(grid_elems((long)c.n * c.ld, 1), 1024);
+    hipLaunchKernelGGL(k_dcon_comb, dim3(grid), dim3(kBlock), 0, st, c.n, c.r, c.ld, c.kd, c.dA_con, w, T, scale, beta,
+                       out + c.foff, dotx ? dotx + c.foff : nullptr, part);
+    LRS_CHECK_LAUNCH();
+    if (nblk) *nblk = grid;
+    return 0;
+}
+int launch_dcon_dots(const DevProblem &P, int cone, const double *T, const double *p, double *out, double *outb,
+                     int accumulate, hipStream_t st) {
+    const DevCone &c = P.cones[cone];
+    hipLaunchKernelGGL(k_dcon_dots, dim3(c.kd), dim3(kBlock), 0, st, c.n, c.r, c.ld, c.dA_con, T, p + c.foff, out, outb,
+                       accumulate);
+    LRS_CHECK_LAUNCH();
     return 0;
 }
 
@@ -7156,9 +7380,13 @@ int launch_ls_only(const DevProblem &P, DevWork &W, hipStream_t st) {
     one[C_ACTIVE] = 1.0;
     if (hipMemcpyAsync(W.ctrl, one, sizeof(one), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     double *fin = fin_ptr();
-    hipLaunchKernelGGL(k_alm_gather_q, dim3(grid_elems(P.m, 1)), dim3(kBlock), 0, st, P.m, P.K, P.con_ptr,
-                       P.con_slot, P.con_w, W.uvt0, W.uvt1, P.b, W.cvs, W.lam, W.par, W.q1, W.q2, W.partB,
-                       ticket_ptr(T_Q), fin + FIN_Q, W.ctrl);
+    if (P.ndensea)
+        hipLaunchKernelGGL(k_ls_red_q, dim3(grid_elems(P.m, 1)), dim3(kBlock), 0, st, P.m, P.b, W.cvs, W.lam, W.par,
+                           W.q1, W.q2, W.partB, ticket_ptr(T_Q), fin + FIN_Q);
+    else
+        hipLaunchKernelGGL(k_alm_gather_q, dim3(grid_elems(P.m, 1)), dim3(kBlock), 0, st, P.m, P.K, P.con_ptr,
+                           P.con_slot, P.con_w, W.uvt0, W.uvt1, P.b, W.cvs, W.lam, W.par, W.q1, W.q2, W.partB,
+                           ticket_ptr(T_Q), fin + FIN_Q, W.ctrl);
     LRS_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_ls_only, dim3(1), dim3(64), 0, st, W.par, P.K, fin, W.lsres);
     LRS_CHECK_LAUNCH();

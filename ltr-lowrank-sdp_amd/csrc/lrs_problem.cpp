@@ -152,6 +152,39 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
         if (a.row != b.row) return a.row < b.row;
         return a.col < b.col;
     });
+    // dense constraint coefficients (lrs_problem.h policy): per cone, the constraints whose merged
+    // entries fill more than 10 % of the lower triangle, strictly (sdpDataMatChooseType,
+    // data/lorads_sdp_data.c:1187-1191), and whether the cone takes the dense-A path
+    std::vector<std::vector<int>> dcons(K);
+    std::vector<char> dpath(K, 0);
+    bool any_dpath = false;
+    {
+        const char *ea = getenv("LRS_DENSE_A");
+        size_t e = 0;
+        for (int k = 0; k < K; ++k) {
+            const int n = dims_all[k];
+            const double fill = 0.1 * (double)((long)n * (n + 1) / 2);
+            long dnz = 0;   // entries of the cone's dense coefficients
+            while (e < raw.size() && raw[e].cone == k) {
+                size_t e1 = e;
+                long cnt = 0;
+                while (e1 < raw.size() && raw[e1].cone == k && raw[e1].con == raw[e].con) {
+                    if (e1 == e || raw[e1].row != raw[e1 - 1].row || raw[e1].col != raw[e1 - 1].col) cnt++;
+                    e1++;
+                }
+                if (raw[e].con > 0 && (double)cnt > fill && !(nLp > 0 && k == K - 1)) {
+                    dcons[k].push_back(raw[e].con);
+                    dnz += cnt;
+                }
+                e = e1;
+            }
+            if (dcons[k].empty() || !allow_dense) continue;
+            if (ea && ea[0] == '0') dpath[k] = 0;
+            else if (ea && ea[0] == '1') dpath[k] = 1;
+            else dpath[k] = dnz >= kDenseAMinEntries;
+            any_dpath = any_dpath || dpath[k];
+        }
+    }
     // auto constant objective (lrs_problem.h policy): every cone's C constant or absent, and
     // the lean single-workgroup layout (R, D at the widest reachable layout + the pattern)
     // within kSmallLdsBudget
@@ -160,7 +193,8 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
         const char *ek = getenv("LRS_CONST_C");
         const char *ev = getenv("LRS_DENSE_C");
         const char *es = getenv("LRS_SMALL");
-        if (allow_dense && nLp == 0 && !ek && !(ev && ev[0] == '0') && !(es && atoi(es) == 0)) {
+        // (a cone on the dense-A path never runs the single-workgroup loop the constant form is for)
+        if (allow_dense && nLp == 0 && !any_dpath && !ek && !(ev && ev[0] == '0') && !(es && atoi(es) == 0)) {
             bool ok = true, any = false;
             long N = 0, Ptot = 0;
             int ldmax = 0, ldmin = 1 << 30, nconst = 0;
@@ -313,8 +347,19 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
         // pattern = unique (row,col), row-major
         std::vector<std::pair<int, int>> pr;
         pr.reserve(me.size());
+        // dense-A path: the dense coefficients out of the pattern too, into the stack c.dA
+        for (int con : dcons[k]) c.dense_con.push_back(con - 1);
+        c.dense_a = dpath[k] != 0;
+        const std::vector<int> &dk = dcons[k];
+        const bool dpk = dpath[k] != 0;
+        auto dense_idx = [&](int con) -> int {   // position in the stack, or -1
+            if (!dpk) return -1;
+            auto it = std::lower_bound(dk.begin(), dk.end(), con);
+            return it != dk.end() && *it == con ? (int)(it - dk.begin()) : -1;
+        };
+        if (dpk) c.dA.assign(dk.size() * (size_t)c.n * c.n, 0.0);
         for (auto &e : me)
-            if (!(c.dense_c && e.con == 0)) pr.push_back({e.row, e.col});
+            if (!(c.dense_c && e.con == 0) && !(e.con > 0 && dense_idx(e.con) >= 0)) pr.push_back({e.row, e.col});
         std::sort(pr.begin(), pr.end());
         pr.erase(std::unique(pr.begin(), pr.end()), pr.end());
         const int P = (int)pr.size();
@@ -350,8 +395,15 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
                 c.Craw[sl] += r.v;
                 c.Chas[sl] = 1;
             } else {
-                const int sl = slot_of(r.row, r.col);
-                c.ent.push_back({r.con - 1, sl, r.v, r.row == r.col});
+                const int dj = dense_idx(r.con);
+                if (dj >= 0) {
+                    double *A = c.dA.data() + (size_t)dj * c.n * c.n;
+                    A[(size_t)r.row * c.n + r.col] = r.v;
+                    A[(size_t)r.col * c.n + r.row] = r.v;
+                } else {
+                    const int sl = slot_of(r.row, r.col);
+                    c.ent.push_back({r.con - 1, sl, r.v, r.row == r.col});
+                }
                 if (r.con != lastCon) {
                     if (lastCon > 0 && cnt > fill) c.denseCoeff = true;
                     c.nnzRows++;
@@ -464,6 +516,12 @@ bool shard_problem(const HostProblem &g, int world, int rank, HostProblem &out, 
         err = "sharded solve: an LP block is not supported (its ADMM update is a sequential column sweep)";
         return false;
     }
+    for (int k = 0; k < K; ++k)
+        if (g.cones[k].dense_a) {
+            // the stack's products A_i X need every row of X and of A_i: not split by rows
+            err = "sharded solve: a cone on the dense constraint-matrix path is not supported (LRS_DENSE_A=0 keeps it on the slots)";
+            return false;
+        }
     for (int k = 0; k < K; ++k)
         if (g.cones[k].n < world) { err = "sharded solve: a cone has fewer rows than shards"; return false; }
     // a constant objective (C = c_alpha J) is sharded as the slot path: every pair with an owned
@@ -1123,7 +1181,8 @@ bool upload_problem(const HostProblem &hp, DevProblem &dp, std::string &err) {
             !dput(&d.adj_col, c.adj_col, err) || !dput(&d.adj_slot, adj_slot_g, err))
             return false;
         // (a constant objective, const_c, is dense_c too: its rank-one form is the kernel's cconst 2)
-        if (c.own1 < 0 && c.n <= kScMaxN && (!c.dense_c || c.const_c) && !upload_small_cg(c, hp.m, d, err))
+        if (c.own1 < 0 && c.n <= kScMaxN && (!c.dense_c || c.const_c) && !c.dense_a &&
+            !upload_small_cg(c, hp.m, d, err))
             return false;
         if (c.n >= kNX && (long)c.adj_col.size() >= (long)kTileMinDeg * c.n) {
             std::vector<int> cs((size_t)c.n * (kNX + 1));
@@ -1285,6 +1344,12 @@ bool upload_problem(const HostProblem &hp, DevProblem &dp, std::string &err) {
             }
             dp.ndense++;
         }
+        if (c.dense_a) {   // dense-A path: the coefficient stack and its constraints
+            d.kd = (int)c.dense_con.size();
+            d.dA_con_h = c.dense_con;
+            if (!dput(&d.dA, c.dA, err) || !dput(&d.dA_con, c.dense_con, err)) return false;
+            dp.ndensea++;
+        }
     }
     return true;
 }
@@ -1298,7 +1363,8 @@ void free_problem(DevProblem &dp) {
     for (auto &c : dp.cones) { f(c.adj_ptr); f(c.adj_low); f(c.adj_col); f(c.adj_slot); f(c.dra); f(c.drb); f(c.Cd); f(c.colseg); f(c.auv_item); f(c.auv_pq); f(c.auv_pos); f(c.auv_val); f(c.sa_item); f(c.sa_sub); f(c.sa_grp); f(c.sa_pq); f(c.sa_slot);
         f(c.sb_blk); f(c.sb_tp); f(c.sb_rp); f(c.sb_ent); f(c.sa_S); f(c.sx_slot);
         f(c.cg_cadj_ptr); f(c.cg_cadj); f(c.cg_cl_con); f(c.cg_cl_ptr); f(c.cg_ce); f(c.cg_sp); f(c.cg_sj);
-        f(c.cg_cc_ptr); f(c.cg_cc); f(c.cg_ce_w); f(c.cg_sa); f(c.cobj_slot); f(c.lp_slot); f(c.lp_nrm2); }
+        f(c.cg_cc_ptr); f(c.cg_cc); f(c.cg_ce_w); f(c.cg_sa); f(c.cobj_slot); f(c.lp_slot); f(c.lp_nrm2);
+        f(c.dA); f(c.dA_con); }
     if (dp.has_merged) {
         f(dp.merged.adj_ptr); f(dp.merged.adj_low); f(dp.merged.adj_col); f(dp.merged.adj_slot);
         f(dp.merged.dra); f(dp.merged.drb);

@@ -37,6 +37,14 @@ struct HostCone {
     // sharded solve: this shard's owned local rows [own0, own1) (own1 < 0: every row, unsharded).
     // The 2-D tiles of the stage kernels then cover the owned rows only.
     int own0 = 0, own1 = -1;
+    // dense constraint coefficients (the reference's SDP_COEFF_DENSE: more than 10 % of the lower
+    // triangle) of a cone on the dense-A path: kept out of the pattern and of `ent`, as a stack of
+    // full n x n row-major symmetric matrices (dA, coefficient j at j n^2) for the FP64 matrix
+    // cores.  dense_con: the 0-based constraints of the cone's dense coefficients, ascending
+    // (whichever path it takes); dense_a: the cone takes the dense-A path.
+    bool dense_a = false;
+    std::vector<int> dense_con;
+    std::vector<double> dA;
     // the LP block (last block of negative size in SDPA) as the diagonal cone at rank 1
     // (build_problem): its columns are the rows, every slot (j, j)
     bool lp = false;
@@ -47,6 +55,13 @@ struct HostCone {
 // cones with n >= kDenseCMinN whose C fills >= 1/4 of the lower triangle (measured: the dense
 // path is 0.86x the slot path at n = 500, 2.2x at n = 2000, scripts/c5b_probe.py).
 constexpr int kDenseCMinN = 1024;
+// Dense constraint-matrix policy: LRS_DENSE_A=0 never (the dense coefficients stay in the slot
+// pattern), =1 every cone with a dense coefficient, unset: cones whose dense coefficients hold
+// at least kDenseAMinEntries lower-triangle entries together.  Measured (scripts/densea_probe.py,
+// k_d = 16 at r = 32): the slot path's trip costs ~1.6 ns per such entry, the
+// dense path's ~0.4 ms of host-driven launches plus the stack passes -- 1.49x the slot path at
+// n = 250 (326 304 entries), 0.31x at n = 120 (75 504).
+constexpr long kDenseAMinEntries = 320000;
 // Constant-objective policy: a block whose C has all n (n + 1) / 2 entries equal can take the
 // rank-one products (any n >= 2).  LRS_CONST_C=1 every such block, =0 none; unset: only when
 // the whole problem fits the single-workgroup inner loop at every rank the solve can reach

@@ -569,7 +569,7 @@ static void free_work(lrs_ctx *c) {
     double *ptrs[] = {W.R, W.D, W.G[0], W.G[1], W.ls[0], W.ly[0], W.ls[1], W.ly[1], W.U, W.V, W.X, W.cg_r,
                       W.cg_p, W.cg_Q, W.cg_b, W.M2, W.uvt0, W.uvt1, W.uvt2, W.S, W.lam, W.cvs, W.q1, W.q2,
                       W.M1, W.wtmp, W.cvc, W.part, W.partB, W.partC, W.ctrl, W.lsres, W.par, W.gram, W.rec, W.R2,
-                      W.cgc, W.tot, W.gl, W.CR, W.CD, W.GP, W.CGK, W.uvp, W.lpw};
+                      W.cgc, W.tot, W.gl, W.CR, W.CD, W.GP, W.CGK, W.uvp, W.lpw, W.dT, W.dSd, W.dpart};
     for (double *p : ptrs)
         if (p) (void)hipFree(p);
     for (double *q : c->ring_s) if (q) (void)hipFree(q);
@@ -652,6 +652,16 @@ static int alloc_work(lrs_ctx *c, const std::vector<int> &ranks) {
     }
     if (P.ndense && (A(&W.CR, NR) || A(&W.CD, NR))) return -1;
     if (P.lp_cone >= 0 && A(&W.lpw, std::max(2L, lp_sweep_scratch(P)))) return -1;   // k_lp_admm, unstaged
+    if (P.ndensea) {   // dense-A cones: the products' stack, one full matrix, the tile partials
+        long nT = 1, nS = 1, nP = 1;
+        for (const DevCone &dc : P.cones) {
+            if (!dc.kd) continue;
+            nT = std::max(nT, (long)dc.kd * dc.n * dc.ld);
+            nS = std::max(nS, (long)dc.n * dc.n);
+            nP = std::max(nP, 2L * dc.kd * dcon_tiles(dc));
+        }
+        if (A(&W.dT, nT) || A(&W.dSd, nS) || A(&W.dpart, nP)) return -1;
+    }
     {   // k_cgemm2's split-K slabs for the large dense cones
         bool big = false;
         for (const DevCone &dc : P.cones) big = big || (dc.dense_c == 1 && dc.n >= 2048);
@@ -772,6 +782,24 @@ static int read_tmpfin2(lrs_ctx *c, int idx1, int n1, int idx2, int n2, double *
 // host-driven operators
 // ------------------------------------------------------------------------
 static int op_dot(lrs_ctx *c, long n, const double *x, const double *y, double *out);
+// Dense constraint coefficients of cone k (DevCone::dA): out[i] += scale
+// <A_i, sym(X Y^T)> = scale <Y, A_i X> (Y null: X X^T) for the cone's dense i, and outb[i] too
+// when given; one pass over the stack (k_dcon_ax), the tiles' partials added in tile order
+static int dense_a_vals(lrs_ctx *c, int k, const double *X, const double *Y, double scale, double *out,
+                        double *outb) {
+    const DevCone &dc = c->dp.cones[k];
+    OPC(launch_dcon_ax(c->dp, k, dc.kd, dc.dA, X, Y ? Y : X, nullptr, c->W.dpart, c->st));
+    OPC(launch_dcon_fin(c->dp, k, c->W.dpart, 0.0, nullptr, scale, out, outb, 1, c->st));
+    return 0;
+}
+// out rows of cone k += scale sum_i w_i A_i X over its dense i: the products T_i = A_i X into
+// W.dT (left there for the caller), then their combination in i order (k_dcon_comb)
+static int dense_a_adj(lrs_ctx *c, int k, const double *w, const double *X, double scale, double *out) {
+    const DevCone &dc = c->dp.cones[k];
+    OPC(launch_dcon_ax(c->dp, k, dc.kd, dc.dA, X, nullptr, c->W.dT, c->W.dpart, c->st));
+    OPC(launch_dcon_comb(c->dp, k, w, c->W.dT, scale, 1.0, out, nullptr, nullptr, nullptr, c->st));
+    return 0;
+}
 // A(X X^T) for every cone -> cvc[k], cvs = sum_k, returns pinf (primalInfeasibility)
 // and the objective <C, X X^T> (unscaled), with X given per-cone rows in factor buffer.
 // blam != nullptr: also b^T lambda (tmpfin TF_DOT), read behind the same sync
@@ -817,6 +845,13 @@ static int op_constr_xx(lrs_ctx *c, const double *X, const double *Y, double *pi
         fin = TF_RESID;
     }
 READ:
+    if (P.ndensea) {
+        // dense coefficients: their values into the sum and the cone's own, then the residual anew
+        for (int k = 0; k < P.K; ++k)
+            if (P.cones[k].kd && dense_a_vals(c, k, X, Y, 1.0, W.cvs, W.cvc + (long)k * P.m)) return -1;
+        OPC(launch_resid(P.m, P.b, W.cvs, c->st, P.cmask));
+        fin = TF_RESID;
+    }
     if (blam) OPC(launch_dot(P.m, P.bprim ? P.bprim : P.b, W.lam, W.part, c->st, nullptr));
     // dense objective: <C, sym X Y^T> = <X, C Y> over the rows C X covers (sharded: the owned
     // rows, summed over the shards), into TF_DOTC + k, read behind the same sync
@@ -852,11 +887,15 @@ static int op_grad(lrs_ctx *c, double rho, double *lag) {
     // dense objective: C R (the inner loop carries it), G += 2 C R, ||G||^2 anew
     for (int k = 0; k < P.K; ++k) {
         const DevCone &dc = P.cones[k];
-        if (!dc.dense_c) continue;
+        if (!dc.dense_c && !dc.kd) continue;
         const long ro = dc.foff + (long)dc.row0 * dc.ld;   // the rows C R covers (sharded: owned)
         double *Gk = W.G[c->gcur] + ro;
-        OPC(launch_dense_cx(P, k, W.R, W.CR, 0.0, c->st));
-        OPC(launch_axpby((long)dc.nown * dc.ld, 2.0, W.CR + ro, 1.0, Gk, c->st));
+        if (dc.dense_c) {
+            OPC(launch_dense_cx(P, k, W.R, W.CR, 0.0, c->st));
+            OPC(launch_axpby((long)dc.nown * dc.ld, 2.0, W.CR + ro, 1.0, Gk, c->st));
+        }
+        // dense coefficients: G += 2 sum_i M1_i A_i R
+        if (dc.kd && dense_a_adj(c, k, W.M1, W.R, 2.0, W.G[c->gcur])) return -1;
         if (op_dot(c, (long)dc.nown * dc.ld, Gk, Gk, &v[k])) return -1;
     }
     double tot = 0.0;
@@ -1158,7 +1197,16 @@ static int dual_infeasibility(lrs_ctx *c, double *l1, double *lmin, int *all_con
             err += lpe;
             continue;
         }
-        if (trl_min(c, k, W.S, &lk, &steps, &iters, &conv)) return -1;
+        // dense coefficients: S_d = -sum_i lambda_i A_i as one full matrix (S is fixed over the
+        // Lanczos's hundreds of products: formed once, multiplied by k_trl_dense)
+        DevCone &dk = c->dp.cones[k];
+        if (dk.kd) {
+            OPC(launch_dcon_wsum(c->dp, k, W.wtmp, W.dSd, c->st));
+            dk.dSd = W.dSd;
+        }
+        const int trc = trl_min(c, k, W.S, &lk, &steps, &iters, &conv);
+        dk.dSd = nullptr;
+        if (trc) return -1;
         c->dinf_steps += steps;
         c->dinf_iters += iters;
         if (lmin) lmin[k] = lk;
@@ -1600,7 +1648,7 @@ constexpr int kSmallMaxGlobal = 16;
 static bool use_small(lrs_ctx *c) {
     const char *e = getenv("LRS_SMALL");
     const int env = e ? atoi(e) : -1;
-    if (sharded(c) || c->lbfgsL != 2 || c->small_off) return false;
+    if (sharded(c) || c->lbfgsL != 2 || c->small_off || c->dp.ndensea) return false;
     if (c->dp.no_lat != 4) {
         if (c->dp.no_lat != 0 || env == 0) return false;
         if (env != 1 && c->dp.mg > kSmallMaxGlobal) return false;
@@ -1634,8 +1682,13 @@ static int xwg_snapshot(lrs_ctx *c, bool save) {
     return 0;
 }
 
+static int run_inner_generic(lrs_ctx *c, const lrs_params *p, double rho, double rctol, double gap, long budget,
+                             InnerIo &io, bool ph1_exit);
 static int run_inner(lrs_ctx *c, const lrs_params *p, double rho, double rctol, double gap, long budget, InnerIo &io,
                      bool ph1_exit = true) {
+    // a cone on the dense-A path: the operator-composed loop, whose operators carry the dense
+    // terms (the fused stage kernels see the slots only)
+    if (c->dp.ndensea) return run_inner_generic(c, p, rho, rctol, gap, budget, io, ph1_exit);
     double par[P_NPAR] = {0};
     par[P_RHO] = rho; par[P_RCTOL] = rctol; par[P_ENDSUB] = p->endALMSubTol; par[P_ENDTAU] = p->endTauTol;
     par[P_PH1TOL] = ph1_exit ? p->phase1Tol : -1.0; par[P_BN1] = c->hp.bNrm1; par[P_BNINF] = c->hp.bNrmInf; par[P_CNINF] = c->hp.cNrmInf;
@@ -1890,6 +1943,13 @@ static int op_q12_fin(lrs_ctx *c, double *p1h, double *p2h) {
     }
     OPC(launch_gather(P, W.uvt0, 2.0, W.q1, nullptr, nullptr, c->st, nullptr));
     OPC(launch_gather(P, W.uvt1, 1.0, W.q2, nullptr, nullptr, c->st, nullptr));
+    // dense coefficients: q2_i = <D, A_i D>, q1_i = 2 <R, A_i D>, one pass over the stack
+    for (int k = 0; k < P.K; ++k) {
+        const DevCone &dc = P.cones[k];
+        if (!dc.kd) continue;
+        OPC(launch_dcon_ax(P, k, dc.kd, dc.dA, W.D, W.R, nullptr, W.dpart, c->st));
+        OPC(launch_dcon_fin(P, k, W.dpart, 1.0, W.q2, 2.0, W.q1, nullptr, 1, c->st));
+    }
     double *fin = c->s_fin;   // this context's finals (the line search reads them)
     double h[64] = {0};
     h[0] = a; h[1] = b;
@@ -1899,7 +1959,7 @@ static int op_q12_fin(lrs_ctx *c, double *p1h, double *p2h) {
 }
 
 static int run_inner_generic(lrs_ctx *c, const lrs_params *p, double rho, double rctol, double gap, long budget,
-                             InnerIo &io, bool ph1_exit = true) {
+                             InnerIo &io, bool ph1_exit) {
     DevProblem &P = c->dp;
     DevWork &W = c->W;
     const int L = p->lbfgsListLength;
@@ -2064,7 +2124,7 @@ ALG_START:
             io.pinf1 = st.pinf1; io.pinfinf = st.pinfinf;
             for (;;) {
                 const long before = st.innerIter;
-                if (p->lbfgsListLength != 2 ? run_inner_generic(c, p, st.rho, rc_tol, st.gap, budget, io)
+                if (p->lbfgsListLength != 2 ? run_inner_generic(c, p, st.rho, rc_tol, st.gap, budget, io, true)
                                            : run_inner(c, p, st.rho, rc_tol, st.gap, budget, io))
                     return -1;
                 st.innerIter = io.inner; localIter = io.local; clearL = io.clear;
@@ -2205,13 +2265,23 @@ static int cg_solve(lrs_ctx *c, int k, const double *Y, double *X, const double 
     auto auv = [&](const double *x, const double *guard) -> int {
         if (shx && c->comm->halo(c, const_cast<double *>(x), c->st)) return -1;
         OPC(launch_auv_con(P, k, 0, x, Y, 1.0, 0, W.wtmp, nullptr, nullptr, c->st, guard));
+        // dense coefficients: <A_i, sym(x Y^T)> = <x, T_i> with the half-step's T_i = A_i Y (W.dT)
+        if (d.kd) OPC(launch_dcon_dots(P, k, W.dT, x, W.wtmp, nullptr, 1, c->st));
         OPC(sync_shared(P, W.wtmp, c->st));
+        return 0;
+    };
+    // Q += sum_i wtmp_i T_i over the dense coefficients; `part`: the fused <x, Q> retaken over the
+    // whole Q (launch_cg_mv's partials hold the slot part only)
+    auto dmv = [&](const double *x, double *part, int *nblk) -> int {
+        if (!d.kd) return 0;
+        OPC(launch_dcon_comb(P, k, W.wtmp, W.dT, 1.0, 1.0, W.cg_Q, part ? x : nullptr, part, part ? nblk : nullptr, c->st));
         return 0;
     };
     OPC(launch_cg_nrm1(nr, bk, W.part, c->st, &nA));
     if (sum(W.part, nA)) return -1;
     if (auv(X, nullptr)) return -1;
     OPC(launch_cg_mv(P, k, W.wtmp, Y, X, W.cg_Q, nullptr, cgc, 0, c->st, &nB));
+    if (dmv(X, nullptr, nullptr)) return -1;
     OPC(launch_cg_resid(nr, bk, Q, r, p, W.partC, cgc, pA, nA, 1, c->st, &nC));
     if (sum(W.partC, nC)) return -1;
     OPC(launch_cg_resid2(nr, r, p, pC, nC, cgc, tol, 0, 1, c->st));
@@ -2225,6 +2295,7 @@ static int cg_solve(lrs_ctx *c, int k, const double *Y, double *X, const double 
             const int par = it & 1;
             if (auv(W.cg_p, cgc)) return -1;
             OPC(launch_cg_mv(P, k, W.wtmp, Y, W.cg_p, W.cg_Q, W.partB, cgc, 1, c->st, &nB));
+            if (dmv(W.cg_p, W.partB, &nB)) return -1;
             if (sum(W.partB, nB)) return -1;
             OPC(launch_cg_upd(nr, xk, r, p, Q, pB, nB, W.partC, cgc, par, it, c->st, &nC));
             if (sum(W.partC, nC)) return -1;
@@ -2233,6 +2304,7 @@ static int cg_solve(lrs_ctx *c, int k, const double *Y, double *X, const double 
             if (restart) {
                 if (auv(X, cgc)) return -1;
                 OPC(launch_cg_mv(P, k, W.wtmp, Y, X, W.cg_Q, nullptr, cgc, 1, c->st, &nB));
+                if (dmv(X, nullptr, nullptr)) return -1;
                 OPC(launch_cg_resid(nr, bk, Q, r, p, W.partC, cgc, nullptr, 0, 0, c->st, &nR));
                 if (sum(W.partC, nR)) return -1;
                 OPC(launch_cg_resid2(nr, r, p, pC, nR, cgc, tol, par, 0, c->st));
@@ -2259,13 +2331,17 @@ static int update_var_one(lrs_ctx *c, int k, double *X, const double *Y, double 
     OPC(launch_wsum(P, W.M1, 1, W.S, c->st));
     OPC(launch_spmm(P, k, W.S, Y, 1.0, Y, -rho, W.M2, nullptr, 0, nullptr, c->st));   // M2 = S Y - rho Y
     OPC(launch_dense_cx(P, k, Y, W.M2, 1.0, c->st));                                     // + C Y (dense objective)
+    // dense coefficients: + sum_i M1_i A_i Y; the products T_i = A_i Y stay in W.dT for the CG
+    // and the refresh (Y is fixed over the half-step: no further pass over the stack)
+    if (d.kd && dense_a_adj(c, k, W.M1, Y, 1.0, W.M2)) return -1;
     OPC(launch_axpby((long)d.n * d.ld, -1.0 / rho, W.M2 + d.foff, 0.0, W.cg_b + d.foff, c->st));
     if (cg_solve(c, k, Y, X, W.cg_b, tol, maxit)) return -1;
     c->cgIterTotal += c->cgIterCone[k];
     return 0;
 }
 
-static int refresh_cone(lrs_ctx *c, int k) {   // lorads_alg_common.c:310-314
+// solved (optional): the side the half-step just solved, W.dT then holding A_i of the other
+static int refresh_cone(lrs_ctx *c, int k, const double *solved = nullptr) {   // lorads_alg_common.c:310-314
     DevProblem &P = c->dp;
     DevWork &W = c->W;
     double *cv = W.cvc + (long)k * P.m;
@@ -2281,6 +2357,12 @@ static int refresh_cone(lrs_ctx *c, int k) {   // lorads_alg_common.c:310-314
         return 0;
     }
     OPC(launch_auv_con(P, k, 0, W.U, W.V, 1.0, 0, cv, nullptr, nullptr, c->st, nullptr, W.cvs));
+    // dense coefficients: <A_i, sym(U V^T)> added to the cone's values and to the sum (whose
+    // update above took off the old values, dense part included)
+    if (P.cones[k].kd) {
+        if (solved) OPC(launch_dcon_dots(P, k, W.dT, solved, cv, W.cvs, 1, c->st));
+        else if (dense_a_vals(c, k, W.U, W.V, 1.0, cv, W.cvs)) return -1;
+    }
     return 0;
 }
 
@@ -2291,6 +2373,7 @@ static int admm_init_constr(lrs_ctx *c) {
     OPC(launch_fill(P.m, 0.0, c->W.cvs, c->st));
     for (int k = 0; k < P.K; ++k) {
         OPC(launch_auv_con(P, k, 0, c->W.U, c->W.V, 1.0, 0, c->W.cvc + (long)k * P.m, nullptr, nullptr, c->st));
+        if (P.cones[k].kd && dense_a_vals(c, k, c->W.U, c->W.V, 1.0, c->W.cvc + (long)k * P.m, nullptr)) return -1;
         OPC(sync_shared(P, c->W.cvc + (long)k * P.m, c->st));
         OPC(launch_axpby(P.m, 1.0, c->W.cvc + (long)k * P.m, 1.0, c->W.cvs, c->st));
     }
@@ -2304,7 +2387,8 @@ static int admm_init_constr(lrs_ctx *c) {
 static bool use_small_cg(lrs_ctx *c, int k) {
     const char *e = getenv("LRS_SMALL_CG");
     const int env = e ? atoi(e) : -1;
-    return env != 0 && !is_lp(c, k) && c->dp.lp_cone < 0 && small_cg_fits(c->dp, k);
+    // (a problem with a cone on the dense-A path: the operator launches, which carry its terms)
+    return env != 0 && !is_lp(c, k) && c->dp.lp_cone < 0 && c->dp.ndensea == 0 && small_cg_fits(c->dp, k);
 }
 static int admm_half_step(lrs_ctx *c, int k, int side, double rho, double tol, int maxit, bool *on_device) {
     if (use_small_cg(c, k)) {
@@ -2314,7 +2398,7 @@ static int admm_half_step(lrs_ctx *c, int k, int side, double rho, double tol, i
     }
     *on_device = false;
     if (update_var_one(c, k, side ? c->W.V : c->W.U, side ? c->W.U : c->W.V, rho, tol, maxit)) return -1;
-    return refresh_cone(c, k);
+    return refresh_cone(c, k, side ? c->W.V : c->W.U);
 }
 
 static int admm_update_var(lrs_ctx *c, double rho, double tol, int maxit) {
@@ -3148,6 +3232,8 @@ int lrs_op_adjoint(lrs_ctx *c, const double *y, int which, double *out, double s
         OPC(launch_dense_cx(P, k, X, W.cg_Q, 0.0, c->st));
         OPC(launch_axpby((long)dc.n * dc.ld, scale, W.cg_Q + dc.foff, 1.0, W.X + dc.foff, c->st));
     }
+    for (int k = 0; k < P.K; ++k)   // dense coefficients: + scale sum_i y_i A_i X
+        if (P.cones[k].kd && dense_a_adj(c, k, W.M1, X, scale, W.X)) return -1;
     return factor_fetch(c, W.X, out);
 }
 
@@ -3490,7 +3576,7 @@ int lrs_alm_last_step(lrs_ctx *c, double *out4, int *newest_pair) {
     out4[0] = c->last_trip[0];
     out4[1] = c->last_trip[1];
     out4[2] = c->last_trip[2];
-    if (L != 2) {   // run_inner_generic: the newest pair was copied to (S0, Y0)
+    if (L != 2 || c->dp.ndensea) {   // run_inner_generic: the newest pair was copied to (S0, Y0)
         out4[3] = c->ring_beta.empty() ? 0.0 : c->ring_beta[hn];
         if (newest_pair) *newest_pair = 0;
         return 0;
@@ -3511,6 +3597,7 @@ int lrs_profile_stages(lrs_ctx *c, const lrs_params *pin, long steps, double *st
     LRS_NEED_LOADED(c);
     LRS_NEED_ARG(pin);
     LRS_NEED_ARG(stage_ms);
+    if (c->dp.ndensea) { set_err("lrs_profile_stages: a cone on the dense constraint-matrix path runs the operator-composed inner loop (no split-iteration stages)"); return -1; }
     lrs_params prm = *pin;
     prm.phase1Tol = 1e-300;
     prm.maxALMIter = 1000000000;
@@ -3536,6 +3623,7 @@ int lrs_profile_stages(lrs_ctx *c, const lrs_params *pin, long steps, double *st
 int lrs_time_stages(lrs_ctx *c, int reps, double *stage_ms) {
     LRS_NEED_STATE(c);
     LRS_NEED_ARG(stage_ms);
+    if (c->dp.ndensea) { set_err("lrs_time_stages: a cone on the dense constraint-matrix path runs the operator-composed inner loop (no split-iteration stages)"); return -1; }
     // Per-launch durations of the split-iteration stages on the current state: each
     // stage is launched `reps` times back to back between two HIP events on the solver
     // stream.  The stages are idempotent for a fixed control block (A reads ctrl[1] and
@@ -3633,6 +3721,58 @@ int lrs_time_dense(lrs_ctx *c, int cone, int reps, double *avg_ms) {
     *avg_ms = ms / std::max(1, reps);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
+    return 0;
+}
+
+// Dense constraint coefficients of a cone (the reference's SDP_COEFF_DENSE rule) and the path
+// the cone took at load (LRS_DENSE_A / the automatic threshold, lrs_problem.h)
+int lrs_dense_a_info(lrs_ctx *c, int cone, int *n_dense, int *on_dense_path, long *stack_bytes) {
+    LRS_NEED_LOADED(c);
+    if (cone < 0 || cone >= c->dp.K) { set_err("dense_a_info: cone %d of %d", cone, c->dp.K); return -1; }
+    const HostCone &h = c->hp.cones[cone];
+    if (n_dense) *n_dense = (int)h.dense_con.size();
+    if (on_dense_path) *on_dense_path = h.dense_a ? 1 : 0;
+    if (stack_bytes) *stack_bytes = h.dense_a ? (long)(h.dense_con.size() * (size_t)h.n * h.n * sizeof(double)) : 0;
+    return 0;
+}
+
+// k_dcon_ax on R over the cone's whole stack (with the dots' finish): reps launches back to back
+int lrs_time_dense_a(lrs_ctx *c, int cone, int reps, double *avg_ms) {
+    if (!c || !avg_ms) { set_err("time_dense_a: null argument"); return -1; }
+    bind(c);
+    if (!c->walloc || cone < 0 || cone >= c->dp.K || !c->dp.cones[cone].kd) {
+        set_err("time_dense_a: cone %d is not on the dense constraint-matrix path (or no ranks set)", cone);
+        return -1;
+    }
+    const DevCone &dc = c->dp.cones[cone];
+    hipEvent_t e0, e1;
+    HIPC(hipEventCreate(&e0));
+    HIPC(hipEventCreate(&e1));
+    OPC(launch_dcon_ax(c->dp, cone, dc.kd, dc.dA, c->W.R, c->W.R, nullptr, c->W.dpart, c->st));
+    HIPC(hipEventRecord(e0, c->st));
+    for (int q = 0; q < reps; ++q)
+        OPC(launch_dcon_ax(c->dp, cone, dc.kd, dc.dA, c->W.R, c->W.R, nullptr, c->W.dpart, c->st));
+    HIPC(hipEventRecord(e1, c->st));
+    HIPC(hipEventSynchronize(e1));
+    float ms = 0;
+    HIPC(hipEventElapsedTime(&ms, e0, e1));
+    *avg_ms = ms / std::max(1, reps);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return 0;
+}
+
+// Host-only: the dense coefficients of the instance at `path` by the reference's rule, per cone
+int lrs_dense_a_plan(const char *path, int cone, int *n_dense, int *on_dense_path, int *cons, int cap) {
+    if (!path) { set_err("null argument"); return -1; }
+    HostProblem g;
+    std::string err;
+    if (!read_sdpa(path, g, err)) { set_err("read_sdpa: %s", err.c_str()); return -1; }
+    if (cone < 0 || cone >= g.K) { set_err("dense_a_plan: cone %d of %d", cone, g.K); return -1; }
+    const HostCone &h = g.cones[cone];
+    if (n_dense) *n_dense = (int)h.dense_con.size();
+    if (on_dense_path) *on_dense_path = h.dense_a ? 1 : 0;
+    for (int j = 0; cons && j < cap && j < (int)h.dense_con.size(); ++j) cons[j] = h.dense_con[j];
     return 0;
 }
 

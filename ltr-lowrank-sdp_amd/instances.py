@@ -10,6 +10,8 @@ restated as a generator with the same structure:
 * Lovász theta: C = -J (dense), tr(X) = 1, X_ij = 0 on edges.
 * random sparse SDP (C5): C = I (or dense), A_i with k random lower entries,
   b_i = <A_i, I> so X = I is feasible.
+* dense constraint matrices: sparse random constraints plus a few A_i that fill a given
+  fraction of the lower triangle (the reference's SDP_COEFF_DENSE, more than 10 %).
 * MaxCut with an LP block (the SDPA negative block size, io/lorads_file_io.c:104-194):
   X_ii + s_i = 1 with LP slacks s_i >= 0, plus LP columns that touch many constraints.
 
@@ -33,6 +35,8 @@ __all__ = [
     "write_sdpa",
     "config_instance",
     "maxcut_lp",
+    "dense_constraints_problem",
+    "dense_constraints",
 ]
 
 
@@ -258,3 +262,53 @@ def maxcut_lp(path, n, p_edge, seed):
     ents.append((np.array([m, m]), 2, np.array([n + 1, n + 2]), np.array([n + 1, n + 2]), np.array([1.0, -1.0])))
     b = np.concatenate([np.ones(n), [0.0]])
     return write_sdpa(path, m, [n, -nlp], b, ents)
+
+
+def dense_constraints_problem(dims, m_sparse, k, fills, cross, seed):
+    """Dense constraint matrices in memory: (m, dims, b, entries).  C = I on every block.  Block b
+    has m_sparse[b] constraints of k random lower-triangle N(0,1) entries (numbered block by
+    block); then block 1 gets one constraint per entry f of `fills` with round(f T) distinct
+    lower-triangle positions, T = n (n + 1) / 2, and N(0,1) values (f = 1.0: all T positions;
+    f = 0.1: exactly floor(0.1 T), which the reference's strict 10 % rule keeps sparse).  The
+    fills constraint of index `cross` (None: none) also has five random entries in block 2.
+    b_i = tr(A_i), so X = I is feasible and, with C = I, the problem is bounded."""
+    rng = np.random.default_rng(seed)
+    dims = [int(d) for d in dims]
+    entries, b = [], []
+    for blk, n in enumerate(dims, start=1):
+        d = np.arange(1, n + 1)
+        entries.append((np.zeros(n, dtype=np.int64), blk, d, d, -np.ones(n)))
+    con0 = 1
+    for blk, (n, ms) in enumerate(zip(dims, m_sparse), start=1):
+        ii = rng.integers(0, n, size=(ms, k))
+        jj = rng.integers(0, n, size=(ms, k))
+        lo, hi = np.minimum(ii, jj), np.maximum(ii, jj)
+        v = rng.standard_normal((ms, k))
+        b += np.where(lo == hi, v, 0.0).sum(axis=1).tolist()
+        entries.append((np.repeat(np.arange(con0, con0 + ms), k), blk, lo.ravel() + 1, hi.ravel() + 1, v.ravel()))
+        con0 += ms
+    n = dims[0]
+    iu, ju = np.triu_indices(n)
+    T = iu.size
+    for t, f in enumerate(fills):
+        cnt = T if f >= 1.0 else (int(np.floor(0.1 * T)) if f == 0.1 else int(round(f * T)))
+        pos = np.sort(rng.choice(T, size=cnt, replace=False))
+        v = rng.standard_normal(cnt)
+        bi = float(v[iu[pos] == ju[pos]].sum())
+        entries.append((np.full(cnt, con0, dtype=np.int64), 1, iu[pos] + 1, ju[pos] + 1, v))
+        if cross is not None and t == cross:
+            n2 = dims[1]
+            i2 = rng.integers(0, n2, size=5)
+            j2 = rng.integers(0, n2, size=5)
+            lo, hi = np.minimum(i2, j2), np.maximum(i2, j2)
+            v2 = rng.standard_normal(5)
+            bi += float(v2[lo == hi].sum())
+            entries.append((np.full(5, con0, dtype=np.int64), 2, lo + 1, hi + 1, v2))
+        b.append(bi)
+        con0 += 1
+    return con0 - 1, dims, np.array(b), entries
+
+
+def dense_constraints(path, dims, m_sparse, k, fills, cross, seed):
+    """dense_constraints_problem written as a .dat-s file."""
+    return write_sdpa(path, *dense_constraints_problem(dims, m_sparse, k, fills, cross, seed))

@@ -130,6 +130,9 @@ def load_library(path=None):
         "lrs_mfma_f64_peak": (C.c_int, [vp, dp]),
         "lrs_mfma_f64_probe": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, dp]),
         "lrs_time_dense": (C.c_int, [vp, C.c_int, C.c_int, dp]),
+        "lrs_dense_a_info": (C.c_int, [vp, C.c_int, ip, ip, C.POINTER(C.c_long)]),
+        "lrs_time_dense_a": (C.c_int, [vp, C.c_int, C.c_int, dp]),
+        "lrs_dense_a_plan": (C.c_int, [C.c_char_p, C.c_int, ip, ip, ip, C.c_int]),
         "lrs_load_coo": (C.c_int, [vp, C.c_int, C.c_int, ip, dp, C.c_long, ip, ip, ip, ip, dp]),
         "lrs_debug_phase_times": (C.c_int, [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
         "lrs_comm_unique_id": (C.c_int, [C.c_char_p]),
@@ -590,6 +593,19 @@ class Solver:
         self._check(self.lib.lrs_time_dense(self.ctx, cone, reps, C.byref(t)), "time_dense")
         return t.value
 
+    def dense_a_info(self, cone=0):
+        """(dense constraint coefficients of `cone`, on the dense-A path, bytes of its stack)
+        (lrs_dense_a_info)."""
+        n, on, nb = C.c_int(), C.c_int(), C.c_long()
+        self._check(self.lib.lrs_dense_a_info(self.ctx, cone, C.byref(n), C.byref(on), C.byref(nb)), "dense_a_info")
+        return n.value, bool(on.value), nb.value
+
+    def time_dense_a(self, cone=0, reps=10):
+        """ms per k_dcon_ax launch over the stack of `cone` on R (lrs_time_dense_a)."""
+        t = C.c_double()
+        self._check(self.lib.lrs_time_dense_a(self.ctx, cone, reps, C.byref(t)), "time_dense_a")
+        return t.value
+
     def mfma_f64_peak(self):
         """Measured FP64 matrix-core TFLOP/s of this device (lrs_mfma_f64_peak)."""
         t = C.c_double()
@@ -608,6 +624,20 @@ class Solver:
         ms = C.c_double()
         self._check(self.lib.lrs_time_auut(self.ctx, reps, C.byref(ms)), "time_auut")
         return ms.value
+
+
+def dense_a_plan(path, cone=0):
+    """Host-only classification of the dense constraint coefficients of `cone` (lrs_dense_a_plan;
+    no device needed): (0-based constraint indices, whether the cone takes the dense-A path)."""
+    lib = load_library()
+    n, on = C.c_int(), C.c_int()
+    if lib.lrs_dense_a_plan(str(path).encode(), cone, C.byref(n), C.byref(on), None, 0) != 0:
+        raise RuntimeError(lib.lrs_last_error().decode())
+    cons = np.zeros(max(1, n.value), dtype=np.int32)
+    if lib.lrs_dense_a_plan(str(path).encode(), cone, C.byref(n), C.byref(on),
+                            cons.ctypes.data_as(C.POINTER(C.c_int)), n.value) != 0:
+        raise RuntimeError(lib.lrs_last_error().decode())
+    return cons[:n.value].tolist(), bool(on.value)
 
 
 def shard_plan(path, world, rank):
