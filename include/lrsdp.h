@@ -276,6 +276,37 @@ int lrs_dense_a_info(lrs_ctx *ctx, int cone, int *n_dense, int *on_dense_path, l
 int lrs_time_dense_a(lrs_ctx *ctx, int cone, int reps, double *avg_ms);
 int lrs_dense_a_plan(const char *path, int cone, int *n_dense, int *on_dense_path, int *cons, int cap);
 
+/* Rank-one dense constraint matrices.  Every coefficient the rule above types
+ * dense is tested for A_i = sigma a a^T (pivot on the largest |A_pp|, accepted iff max |A_jk -
+ * sigma a_j a_k| <= 1e-13 max|A|).  A cone that factors them keeps V = [a_1 .. a_p] (n x p) in
+ * place of p full matrices -- n p doubles, not p n^2 -- and evaluates them as skinny products on
+ * the FP64 matrix cores (k_r1_vtx, k_r1_apply).  LRS_RANK1_A=0: no detection; =1: every cone with
+ * such a coefficient factors them (its other dense coefficients follow LRS_DENSE_A); unset: the
+ * cones LRS_DENSE_A selects factor theirs.  Read when a problem is loaded.  Such a cone runs the
+ * operator-composed inner loop, and sharded contexts refuse it, as for the dense-A path.
+ * lrs_dense_a_info's n_dense still counts these coefficients; its stack_bytes does not.
+ * lrs_rank1_info: the cone's number of rank-one dense coefficients (whichever path; 0 under
+ * LRS_RANK1_A=0), whether it keeps a factor, and the factor's bytes (0 without); outputs may be
+ * NULL.
+ * lrs_rank1_plan: host-only (no device, no context) detection on the instance at `path`: cons and
+ * sigma (each may be NULL) receive up to cap 0-based constraint indices, ascending, and signs.
+ * lrs_time_rank1: ms per V^T R launch (k_r1_vtx with its finish) averaged over `reps` back-to-back
+ * launches, and that launch's algorithmic bytes n (ldp + ld) 8 (may be NULL); fails when the cone
+ * has no factor.
+ * lrs_load_coo_rank1: lrs_load_coo plus nterm terms tsigma[t] a_t a_t^T on (constraint tcon[t] >=
+ * 1, SDP block tblk[t], 1-based), the vectors concatenated in tvec, each of length dims[tblk[t]].
+ * Refused: a term on constraint 0 (the objective), a term in the LP block, a (constraint, block)
+ * that also has explicit entries.  A term whose expansion the reference's rule types sparse (z
+ * nonzeros in a, z (z + 1) / 2 <= 0.1 n (n + 1) / 2) is expanded into entries and takes the slot
+ * path; every other term is factored whatever LRS_RANK1_A says, and its n^2 entries are never
+ * formed.  Ranks and norms come out as for the expanded entries. */
+int lrs_rank1_info(lrs_ctx *ctx, int cone, int *n_rank1, int *on_factor_path, long *factor_bytes);
+int lrs_rank1_plan(const char *path, int cone, int *n_rank1, int *on_factor_path, int *cons, double *sigma, int cap);
+int lrs_time_rank1(lrs_ctx *ctx, int cone, int reps, double *avg_ms, double *bytes);
+int lrs_load_coo_rank1(lrs_ctx *ctx, int m, int nblk, const int *dims, const double *b, long nnz, const int *con,
+                       const int *blk, const int *row, const int *col, const double *val, int nterm, const int *tcon,
+                       const int *tblk, const double *tsigma, const double *tvec);
+
 /* Per-stage timing of the split ALM inner iteration: runs `steps` inner iterations at
  * the current rank like lrs_alm_throughput, with HIP events on the solver stream
  * around each of the four launches (S1 direction+SDDMM, S2 q-gather, S3 update+

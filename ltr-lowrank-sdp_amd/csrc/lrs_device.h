@@ -126,6 +126,16 @@ struct DevCone {
     int *dA_con = nullptr;
     std::vector<int> dA_con_h;
     const double *dSd = nullptr;         // while the dual infeasibility runs: S_d = -sum_j lambda_j A_j (n x n)
+    // rank-one dense coefficients (lrs_problem.h HostCone::rV), in neither the slots nor the stack:
+    // rV n x rldp row-major (row i: a_1[i] .. a_rp[i], padding 0; rldp a multiple of 16), term t
+    // = r_sigma[t] a_t a_t^T of constraint r_con[t] (ascending)
+    int rp = 0, rldp = 0;
+    double *rV = nullptr, *r_sigma = nullptr;
+    int *r_con = nullptr;
+    // while the dual infeasibility runs: the weights w (S_r = sum_t w[con_t] sigma_t a_t a_t^T),
+    // a p-vector for V^T v and k_r1_vtx's chunk partials
+    const double *r1w = nullptr;
+    double *r1T = nullptr, *r1part = nullptr;
     // long rows (>= kTileMinDeg adjacency entries per row on average): per row, the first entry
     // at or past column x n / kNX, x = 0..kNX ([n][kNX + 1]); the column-tiled k_wide_* kernels
     int *colseg = nullptr;
@@ -252,7 +262,7 @@ struct DevProblem {
     double *spack = nullptr;                                 // [nsh] one m-vector's shared entries
     std::vector<DevCone> cones;
     int ndense = 0;                                          // cones with a dense objective (DevCone::Cd)
-    int ndensea = 0;                                         // cones on the dense-A path (DevCone::dA)
+    int ndensea = 0;                                         // cones on the dense-A path (DevCone::dA) or with a rank-one factor (DevCone::rV)
     bool tiles = false;                                      // column-tiled long-row kernels (LRS_TILES=1 at alloc)
     double *gp = nullptr;                                    // DevWork::GP (kNX partial factors), the tiled S X's scratch
     double *cgk = nullptr;                                   // DevWork::CGK: k_cgemm2's split-K slabs (kCgSplitSlabs x NRpad)
@@ -275,6 +285,10 @@ struct DevWork {
     // dense-A cones (DevCone::dA), sized for the largest: dT the products T_i = A_i X (kd x n x ld),
     // dSd one full matrix sum_i w_i A_i (n x n), dpart k_dcon_ax's tile partials
     double *dT = nullptr, *dSd = nullptr, *dpart = nullptr;
+    // cones with a rank-one factor (DevCone::rV), sized for the largest: rTx, rTz the products
+    // V^T X, V^T Z (rldp x ld each), rTy V^T Y of the ADMM half-step (kept over its CG), rpart
+    // k_r1_vtx's chunk partials
+    double *rTx = nullptr, *rTz = nullptr, *rTy = nullptr, *rpart = nullptr;
     // column-tiled long-row kernels: kNX partial S R_new factors (kNX * NRpad), null when no cone
     // has long rows
     double *GP = nullptr;
@@ -375,6 +389,21 @@ int launch_dcon_comb(const DevProblem &P, int cone, const double *w, const doubl
 // out[con_i] (+)= <p, T_i>, outb[con_i] += it (optional)
 int launch_dcon_dots(const DevProblem &P, int cone, const double *T, const double *p, double *out, double *outb,
                      int accumulate, hipStream_t st);
+// rank-one dense coefficients of a cone (DevCone::rV, rp terms; lrs_kernels.hip "rank-one dense
+// coefficients").  launch_r1_vtx: Tx = V^T X and, with Z, Tz = V^T Z in the same
+// pass over V (X, Z cone-local, n x ld, r columns; Tx, Tz rldp x ld); part: r1_part_len doubles.
+// launch_r1_vals: per term t, v0 = sigma_t <Tx_t, Tx_t>, v1 = sigma_t <Tx_t, Tz_t> (Tz null: Tx);
+// out0[con_t] (+)= s0 v0, out1[con_t] (+)= s1 v1, out1b[con_t] += s1 v1 (each optional), a
+// constraint's terms in index order.  launch_r1_apply: out = beta out + scale V diag(w[con_t]
+// sigma_t) T on the cone's rows (out, dotx cone-local); with dotx and part: the blocks' partial
+// <dotx, out> in part[0 .. *nblk) (launch_cg_mv's layout).
+long r1_part_len(const DevCone &c, int r);
+int launch_r1_vtx(const DevCone &c, int r, int ld, const double *X, const double *Z, double *Tx, double *Tz,
+                  double *part, hipStream_t st);
+int launch_r1_vals(const DevCone &c, int r, int ld, const double *Tx, const double *Tz, double s0, double *out0,
+                   double s1, double *out1, double *out1b, int accumulate, hipStream_t st);
+int launch_r1_apply(const DevCone &c, int r, int ld, const double *w, const double *T, double scale, double beta,
+                    double *out, const double *dotx, double *part, int *nblk, hipStream_t st);
 int dense_cd_blocks(const DevProblem &P);
 int launch_dense_cd(const DevProblem &P, const DevWork &W, const double *ctrl, int off, hipStream_t st);
 

@@ -4382,6 +4382,14 @@ int launch_trl_symv(const DevProblem &P, int cone, const double *S, const double
         hipLaunchKernelGGL(k_trl_dense, dim3(grid), dim3(kBlock), 0, st, c.n, c.n, 0, 1.0, c.dSd, vj ? vj : x, y);
         LRS_CHECK_LAUNCH();
     }
+    if (c.r1w) {   // rank-one factor: y += V diag(w sigma) (V^T v), the two factor kernels at r = 1 (no n x n matrix)
+        if (!vj && b2) {
+            snprintf(g_err, sizeof(g_err), "trl: a cone with a rank-one factor needs the normalized vector");
+            return -1;
+        }
+        if (launch_r1_vtx(c, 1, 1, vj ? vj : x, nullptr, c.r1T, nullptr, c.r1part, st)) return -1;
+        if (launch_r1_apply(c, 1, 1, c.r1w, c.r1T, 1.0, 1.0, y, nullptr, nullptr, nullptr, st)) return -1;
+    }
     return 0;
 }
 
@@ -5675,6 +5683,191 @@ int launch_dcon_dots(const DevProblem &P, int cone, const double *T, const doubl
     hipLaunchKernelGGL(k_dcon_dots, dim3(c.kd), dim3(kBlock), 0, st, c.n, c.r, c.ld, c.dA_con, T, p + c.foff, out, outb,
                        accumulate);
     LRS_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- rank-one dense coefficients A_t = sigma_t a_t a_t^T as a factor: V =
+// [a_1 .. a_p] row-major n x ldp (DevCone::rV, padding 0, ldp a multiple of 16).  Everything the
+// solver needs is a skinny product: <A_t, sym(X Z^T)> = sigma_t <(V^T X)_t, (V^T Z)_t>, and
+// A^*(w) X = V diag(w sigma) (V^T X) -- n p doubles in place of the stack's p n^2.
+// k_r1_vtx: T = V^T X (p x r) and, with Z, V^T Z in the same pass over V.  k_gram's scheme with
+// two different operands: grid (C row chunks) x (16-term tiles x 16-column tiles); the four waves
+// take interleaved 4-row k-steps of the chunk (rows past its end read as 0), lane l feeding the
+// MFMA V[row][16 pt + (l & 15)] and X[row][16 rt + (l & 15)], row = k-step's first + (l >> 4); the
+// waves' accumulators meet in LDS in wave order and the chunk's partial tile goes to part.  A
+// column at or past ld is read from the row's last one (it only reaches its own, unstored, output
+// column).  k_r1_vtx_fin adds the C partials of every element in chunk order and stores terms x
+// columns < r (D fragment: col = l & 15, row = (l >> 4) + 4 q).  No atomics: bitwise reproducible.
+constexpr int kR1MaxChunks = 64;
+template <bool HASZ>
+__global__ void __launch_bounds__(kBlock) k_r1_vtx(int n, int ld, int ldp, int per, int nrt,
+                                                   const double *__restrict__ V, const double *__restrict__ X,
+                                                   const double *__restrict__ Z, double *__restrict__ part) {
+    constexpr int NW = HASZ ? 2 : 1;
+    __shared__ double red[kBlock / 64][NW][256];
+    const int tile = blockIdx.y, pt = tile / nrt, rt = tile % nrt;
+    const int C = gridDim.x, ch = blockIdx.x;
+    const int i0 = ch * per, i1 = min(n, i0 + per);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int colV = 16 * pt + (lane & 15), colX = min(16 * rt + (lane & 15), ld - 1);
+    gram_acc_t ax = gram_acc_t{0.0, 0.0, 0.0, 0.0}, az = gram_acc_t{0.0, 0.0, 0.0, 0.0};
+    const int nk = i1 > i0 + 4 * w ? (i1 - i0 - 4 * w + 15) / 16 : 0;
+#pragma unroll 4
+    for (int j = 0; j < nk; ++j) {
+        const int row = i0 + 16 * j + 4 * w + (lane >> 4);
+        const bool ok = row < i1;
+        const long rr = ok ? row : i0;
+        double v = V[rr * ldp + colV], x = X[rr * ld + colX];
+        v = ok ? v : 0.0;
+        x = ok ? x : 0.0;
+        ax = __builtin_amdgcn_mfma_f64_16x16x4f64(v, x, ax, 0, 0, 0);
+        if constexpr (HASZ) {
+            double z = Z[rr * ld + colX];
+            z = ok ? z : 0.0;
+            az = __builtin_amdgcn_mfma_f64_16x16x4f64(v, z, az, 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        red[w][0][q * 64 + lane] = ax[q];
+        if constexpr (HASZ) red[w][1][q * 64 + lane] = az[q];
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        double s = red[0][k][t];
+#pragma unroll
+        for (int ww = 1; ww < kBlock / 64; ++ww) s += red[ww][k][t];
+        part[(((long)tile * NW + k) * C + ch) * 256 + t] = s;
+    }
+}
+// a thread an element of a (tile, product): the chunks' partials in chunk order
+__global__ void __launch_bounds__(kBlock) k_r1_vtx_fin(int r, int ld, int nrt, int ntile, int NW, int C,
+                                                       const double *__restrict__ part, double *__restrict__ Tx,
+                                                       double *__restrict__ Tz) {
+    const long id = (long)blockIdx.x * kBlock + threadIdx.x;
+    if (id >= (long)ntile * NW * 256) return;
+    const int t = (int)(id & 255), k = (int)((id >> 8) % NW), tile = (int)((id >> 8) / NW);
+    double s = 0.0;
+    for (int ch = 0; ch < C; ++ch) s += part[(((long)tile * NW + k) * C + ch) * 256 + t];
+    const int q = t >> 6, l = t & 63;
+    const int term = 16 * (tile / nrt) + (l >> 4) + 4 * q, col = 16 * (tile % nrt) + (l & 15);
+    if (col < r) (k ? Tz : Tx)[(long)term * ld + col] = s;
+}
+// per term t: v0 = sigma_t <Tx_t, Tx_t>, v1 = sigma_t <Tx_t, Tz_t>, added over the consecutive
+// terms of one constraint in index order (a thread a constraint's run of terms); out0[con] (+)=
+// s0 v0, out1[con] (+)= s1 v1, out1b[con] += s1 v1 (each optional), as k_dcon_fin
+__global__ void __launch_bounds__(kBlock) k_r1_vals(int p, int r, int ld, const int *__restrict__ con,
+                                                    const double *__restrict__ sigma, const double *__restrict__ Tx,
+                                                    const double *__restrict__ Tz, double s0, double *out0, double s1,
+                                                    double *out1, double *out1b, int accumulate) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= p) return;
+    const int i = con[t];
+    if (t > 0 && con[t - 1] == i) return;
+    double v0 = 0.0, v1 = 0.0;
+    for (int u = t; u < p && con[u] == i; ++u) {
+        double d0 = 0.0, d1 = 0.0;
+        for (int j = 0; j < r; ++j) {
+            const double x = Tx[(long)u * ld + j];
+            d0 += x * x;
+            d1 += x * Tz[(long)u * ld + j];
+        }
+        v0 += sigma[u] * d0;
+        v1 += sigma[u] * d1;
+    }
+    if (out0) out0[i] = (accumulate ? out0[i] : 0.0) + s0 * v0;
+    if (out1) out1[i] = (accumulate ? out1[i] : 0.0) + s1 * v1;
+    if (out1b) out1b[i] += s1 * v1;
+}
+// k_r1_apply: out = beta out + scale V diag(w[con_t] sigma_t) T on the cone's n x ld rows
+// (columns < r): an n x r GEMM with K = p on the matrix cores.  A wave a 16 x 16 output tile
+// (tiles wave-strided over the grid), K in steps of 4: A[i][k] = V[row i][k], B[k][j] = w sigma_k
+// T[k][j] (0 past p and past r).  With dotx, the block's partial <dotx, out> into
+// part[blockIdx.x] (the CG's fused <p, Q>, launch_cg_mv's layout).  One wave an element, fixed
+// order: bitwise reproducible.
+__global__ void __launch_bounds__(kBlock) k_r1_apply(int n, int r, int ld, int p, int ldp, int nrt,
+                                                     const double *__restrict__ V, const int *__restrict__ con,
+                                                     const double *__restrict__ sigma, const double *__restrict__ w,
+                                                     const double *__restrict__ T, double scale, double beta,
+                                                     double *__restrict__ out, const double *__restrict__ dotx,
+                                                     double *__restrict__ part) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int units = ((n + 15) / 16) * nrt;
+    double dacc[1] = {0.0};
+    for (int u = blockIdx.x * (kBlock / 64) + wv; u < units; u += gridDim.x * (kBlock / 64)) {
+        const int row = 16 * (u / nrt) + (lane & 15), col = 16 * (u % nrt) + (lane & 15);
+        const bool rok = row < n, cok = col < r;
+        const double *__restrict__ Vr = V + (long)(rok ? row : 0) * ldp;
+        gram_acc_t acc = gram_acc_t{0.0, 0.0, 0.0, 0.0};
+        for (int k0 = 0; k0 < ldp; k0 += 4) {
+            const int k = k0 + (lane >> 4);
+            const double a = rok ? Vr[k] : 0.0;
+            double b = 0.0;
+            if (k < p && cok) b = (w[con[k]] * sigma[k]) * T[(long)k * ld + col];
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int orow = 16 * (u / nrt) + (lane >> 4) + 4 * q;
+            if (orow < n && cok) {
+                const long o = (long)orow * ld + col;
+                const double v = (beta != 0.0 ? beta * out[o] : 0.0) + scale * acc[q];
+                out[o] = v;
+                if (dotx) dacc[0] += dotx[o] * v;
+            }
+        }
+    }
+    if (part) write_partials<1>(dacc, part, blockIdx.x);
+}
+// row chunks of k_r1_vtx: k_gram's policy (rows per chunk a multiple of 16, at most kR1MaxChunks
+// chunks, about 1024 workgroups in all); LRS_R1_CHUNK=<rows per chunk> (tests: chunk boundaries
+// at small n), read at launch
+static int r1_chunk_rows(int n, int ntile) {
+    const int gx = std::max(1, std::min({kR1MaxChunks, (n + 63) / 64, std::max(8, 1024 / std::max(1, ntile))}));
+    int per = ((n + gx - 1) / gx + 15) / 16 * 16;
+    if (const char *e = getenv("LRS_R1_CHUNK")) {
+        const int v = (atoi(e) + 15) / 16 * 16;
+        if (v >= 16 && (n + v - 1) / v <= kR1MaxChunks) per = v;
+    }
+    return per;
+}
+long r1_part_len(const DevCone &c, int r) {
+    return (long)(c.rldp / 16) * ((std::max(1, r) + 15) / 16) * 2 * kR1MaxChunks * 256;
+}
+int launch_r1_vtx(const DevCone &c, int r, int ld, const double *X, const double *Z, double *Tx, double *Tz,
+                  double *part, hipStream_t st) {
+    const int nrt = (r + 15) / 16, ntile = (c.rldp / 16) * nrt;
+    const int per = r1_chunk_rows(c.n, ntile), C = (c.n + per - 1) / per;
+    if (Z)
+        hipLaunchKernelGGL(k_r1_vtx<true>, dim3(C, ntile), dim3(kBlock), 0, st, c.n, ld, c.rldp, per, nrt, c.rV, X, Z,
+                           part);
+    else
+        hipLaunchKernelGGL(k_r1_vtx<false>, dim3(C, ntile), dim3(kBlock), 0, st, c.n, ld, c.rldp, per, nrt, c.rV, X, Z,
+                           part);
+    LRS_CHECK_LAUNCH();
+    const int NW = Z ? 2 : 1;
+    hipLaunchKernelGGL(k_r1_vtx_fin, dim3((ntile * NW * 256 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, r, ld, nrt,
+                       ntile, NW, C, part, Tx, Tz);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_r1_vals(const DevCone &c, int r, int ld, const double *Tx, const double *Tz, double s0, double *out0,
+                   double s1, double *out1, double *out1b, int accumulate, hipStream_t st) {
+    hipLaunchKernelGGL(k_r1_vals, dim3((c.rp + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c.rp, r, ld, c.r_con,
+                       c.r_sigma, Tx, Tz ? Tz : Tx, s0, out0, s1, out1, out1b, accumulate);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_r1_apply(const DevCone &c, int r, int ld, const double *w, const double *T, double scale, double beta,
+                    double *out, const double *dotx, double *part, int *nblk, hipStream_t st) {
+    const int nrt = (r + 15) / 16, units = ((c.n + 15) / 16) * nrt;
+    const int grid = std::max(1, std::min((units + kBlock / 64 - 1) / (kBlock / 64), 1024));
+    hipLaunchKernelGGL(k_r1_apply, dim3(grid), dim3(kBlock), 0, st, c.n, r, ld, c.rp, c.rldp, nrt, c.rV, c.r_con,
+                       c.r_sigma, w, T, scale, beta, out, dotx, part);
+    LRS_CHECK_LAUNCH();
+    if (nblk) *nblk = grid;
     return 0;
 }
 

@@ -34,7 +34,35 @@ bool is_sep(char c) {
 }  // namespace
 
 static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, bool lpEntries,
-                          std::vector<RawEntry> &raw, HostProblem &hp, std::string &err, bool allow_dense = true);
+                          std::vector<RawEntry> &raw, HostProblem &hp, std::string &err, bool allow_dense = true,
+                          const std::vector<Rank1Term> *terms = nullptr);
+
+// Rank-one test of one dense coefficient (lrs_problem.h policy): its sorted raw entries
+// [e0, e1) (duplicates summed, as the merge does) into the scratch matrix A (n x n), then the
+// pivot rule.  O(n^2).
+static bool detect_rank1(const std::vector<RawEntry> &raw, size_t e0, size_t e1, int n, std::vector<double> &A,
+                         double &sigma, std::vector<double> &a) {
+    A.assign((size_t)n * n, 0.0);
+    for (size_t e = e0; e < e1; ++e) A[(size_t)raw[e].row * n + raw[e].col] += raw[e].v;
+    for (int j = 0; j < n; ++j)
+        for (int k = 0; k < j; ++k) A[(size_t)k * n + j] = A[(size_t)j * n + k];
+    int pv = 0;
+    double amax = 0.0;
+    for (int j = 0; j < n; ++j)
+        if (std::fabs(A[(size_t)j * n + j]) > std::fabs(A[(size_t)pv * n + pv])) pv = j;
+    const double d = A[(size_t)pv * n + pv];
+    if (d == 0.0) return false;
+    for (double v : A) amax = std::max(amax, std::fabs(v));
+    sigma = d > 0.0 ? 1.0 : -1.0;
+    const double s = std::sqrt(std::fabs(d));
+    a.resize(n);
+    for (int j = 0; j < n; ++j) a[j] = A[(size_t)j * n + pv] / s;
+    const double bar = kRank1Tol * amax;
+    for (int j = 0; j < n; ++j)
+        for (int k = 0; k <= j; ++k)
+            if (!(std::fabs(A[(size_t)j * n + k] - sigma * a[j] * a[k]) <= bar)) return false;
+    return true;
+}
 
 bool read_sdpa(const std::string &path, HostProblem &hp, std::string &err) {
     FILE *f = fopen(path.c_str(), "rb");
@@ -126,7 +154,8 @@ bool read_sdpa(const std::string &path, HostProblem &hp, std::string &err) {
 // allow_dense = false (a shard's local problem): every objective entry stays in the slot
 // pattern; shard_problem installs a dense cone's owned row block itself.
 static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, bool lpEntries,
-                          std::vector<RawEntry> &raw, HostProblem &hp, std::string &err, bool allow_dense) {
+                          std::vector<RawEntry> &raw, HostProblem &hp, std::string &err, bool allow_dense,
+                          const std::vector<Rank1Term> *terms) {
     (void)lpEntries;
     // An LP block of nLp columns (x_j = r_j^2, data/lorads_lp_conic.c) is the diagonal SDP cone
     // of nLp rows at rank 1: X = r r^T has X_jj = r_j^2, and the LP data (objective c_j,
@@ -155,11 +184,19 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
     // dense constraint coefficients (lrs_problem.h policy): per cone, the constraints whose merged
     // entries fill more than 10 % of the lower triangle, strictly (sdpDataMatChooseType,
     // data/lorads_sdp_data.c:1187-1191), and whether the cone takes the dense-A path
-    std::vector<std::vector<int>> dcons(K);
-    std::vector<char> dpath(K, 0);
+    // Rank-one coefficients among them (detect_rank1; LRS_RANK1_A, lrs_problem.h policy): r1det
+    // the accepted ones per cone, r1sel whether the cone factors them, scons the constraints left
+    // for the stack.  Terms passed in (lrs_load_coo_rank1) are factored whatever the policy says.
+    struct R1 { int con; double sigma; std::vector<double> a; };
+    std::vector<std::vector<int>> dcons(K), scons(K);
+    std::vector<std::vector<R1>> r1det(K);
+    std::vector<char> dpath(K, 0), r1sel(K, 0);
     bool any_dpath = false;
     {
         const char *ea = getenv("LRS_DENSE_A");
+        const char *er = getenv("LRS_RANK1_A");
+        const bool detect = allow_dense && !(er && er[0] == '0');
+        std::vector<double> scratch;
         size_t e = 0;
         for (int k = 0; k < K; ++k) {
             const int n = dims_all[k];
@@ -175,6 +212,11 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
                 if (raw[e].con > 0 && (double)cnt > fill && !(nLp > 0 && k == K - 1)) {
                     dcons[k].push_back(raw[e].con);
                     dnz += cnt;
+                    if (detect) {
+                        R1 t;
+                        t.con = raw[e].con;
+                        if (detect_rank1(raw, e, e1, n, scratch, t.sigma, t.a)) r1det[k].push_back(std::move(t));
+                    }
                 }
                 e = e1;
             }
@@ -182,8 +224,16 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
             if (ea && ea[0] == '0') dpath[k] = 0;
             else if (ea && ea[0] == '1') dpath[k] = 1;
             else dpath[k] = dnz >= kDenseAMinEntries;
-            any_dpath = any_dpath || dpath[k];
+            r1sel[k] = !r1det[k].empty() && ((er && er[0] == '1') || dpath[k]);
+            if (dpath[k])
+                for (int con : dcons[k]) {
+                    bool factored = false;
+                    for (const R1 &t : r1det[k]) factored = factored || (r1sel[k] && t.con == con);
+                    if (!factored) scons[k].push_back(con);
+                }
+            any_dpath = any_dpath || !scons[k].empty() || r1sel[k];
         }
+        if (terms && !terms->empty()) any_dpath = true;
     }
     // auto constant objective (lrs_problem.h policy): every cone's C constant or absent, and
     // the lean single-workgroup layout (R, D at the widest reachable layout + the pattern)
@@ -349,17 +399,64 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
         pr.reserve(me.size());
         // dense-A path: the dense coefficients out of the pattern too, into the stack c.dA
         for (int con : dcons[k]) c.dense_con.push_back(con - 1);
-        c.dense_a = dpath[k] != 0;
-        const std::vector<int> &dk = dcons[k];
-        const bool dpk = dpath[k] != 0;
+        const std::vector<int> &dk = scons[k];
+        const bool dpk = !dk.empty();
+        c.dense_a = dpk;
+        for (int con : dk) c.stack_con.push_back(con - 1);
         auto dense_idx = [&](int con) -> int {   // position in the stack, or -1
             if (!dpk) return -1;
             auto it = std::lower_bound(dk.begin(), dk.end(), con);
             return it != dk.end() && *it == con ? (int)(it - dk.begin()) : -1;
         };
         if (dpk) c.dA.assign(dk.size() * (size_t)c.n * c.n, 0.0);
+        // rank-one coefficients: the detected ones of a cone that factors them and the terms
+        // passed in, by constraint (stable: a constraint's terms keep their order), into rV
+        std::vector<int> r1k;   // 1-based constraints of the detected coefficients that leave the entries
+        {
+            std::vector<const R1 *> tl;
+            std::vector<R1> given;
+            for (const R1 &t : r1det[k]) { c.r1_con.push_back(t.con - 1); c.r1_sig.push_back(t.sigma); }
+            if (r1sel[k])
+                for (const R1 &t : r1det[k]) { tl.push_back(&t); r1k.push_back(t.con); }
+            if (terms)
+                for (const Rank1Term &t : *terms)
+                    if (t.cone == k) given.push_back({t.con, t.sigma, t.a});
+            for (const R1 &t : given) tl.push_back(&t);
+            std::stable_sort(tl.begin(), tl.end(), [](const R1 *x, const R1 *y) { return x->con < y->con; });
+            if (!tl.empty()) {
+                c.r1_path = true;
+                c.rp = (int)tl.size();
+                c.rldp = (c.rp + 15) / 16 * 16;
+                c.rV.assign((size_t)c.n * c.rldp, 0.0);
+                for (int t = 0; t < c.rp; ++t) {
+                    c.r_con.push_back(tl[t]->con - 1);
+                    c.r_sigma.push_back(tl[t]->sigma);
+                    for (int i = 0; i < c.n; ++i) c.rV[(size_t)i * c.rldp + t] = tl[t]->a[i];
+                }
+                // a term passed in has no entries: its constraint counts among the cone's
+                // coefficients (nnzRows, once per constraint) and types dense
+                std::vector<std::pair<int, double>> rs;
+                for (size_t t = 0; t < c.r1_con.size(); ++t) rs.push_back({c.r1_con[t], c.r1_sig[t]});
+                for (const R1 &t : given) {
+                    if (std::find(c.dense_con.begin(), c.dense_con.end(), t.con - 1) != c.dense_con.end()) continue;
+                    c.nnzRows++;
+                    c.denseCoeff = true;
+                    c.dense_con.push_back(t.con - 1);
+                    rs.push_back({t.con - 1, t.sigma});
+                }
+                std::sort(c.dense_con.begin(), c.dense_con.end());
+                std::stable_sort(rs.begin(), rs.end(), [](const std::pair<int, double> &x, const std::pair<int, double> &y) {
+                    return x.first < y.first;
+                });
+                c.r1_con.clear();
+                c.r1_sig.clear();
+                for (auto &x : rs) { c.r1_con.push_back(x.first); c.r1_sig.push_back(x.second); }
+            }
+        }
+        auto r1_idx = [&](int con) { return std::binary_search(r1k.begin(), r1k.end(), con); };
         for (auto &e : me)
-            if (!(c.dense_c && e.con == 0) && !(e.con > 0 && dense_idx(e.con) >= 0)) pr.push_back({e.row, e.col});
+            if (!(c.dense_c && e.con == 0) && !(e.con > 0 && (dense_idx(e.con) >= 0 || r1_idx(e.con))))
+                pr.push_back({e.row, e.col});
         std::sort(pr.begin(), pr.end());
         pr.erase(std::unique(pr.begin(), pr.end()), pr.end());
         const int P = (int)pr.size();
@@ -400,6 +497,8 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
                     double *A = c.dA.data() + (size_t)dj * c.n * c.n;
                     A[(size_t)r.row * c.n + r.col] = r.v;
                     A[(size_t)r.col * c.n + r.row] = r.v;
+                } else if (r1_idx(r.con)) {
+                    // in the factor rV: counted below from its entries like any other coefficient
                 } else {
                     const int sl = slot_of(r.row, r.col);
                     c.ent.push_back({r.con - 1, sl, r.v, r.row == r.col});
@@ -474,6 +573,14 @@ static bool build_problem(int m, int K, const std::vector<int> &dims, int nLp, b
 bool build_problem_coo(int m, int nblk, const int *dims_in, const double *b, long nnz, const int *con,
                        const int *blk, const int *row, const int *col, const double *val, HostProblem &hp,
                        std::string &err) {
+    return build_problem_coo_rank1(m, nblk, dims_in, b, nnz, con, blk, row, col, val, 0, nullptr, nullptr, nullptr,
+                                   nullptr, hp, err);
+}
+
+bool build_problem_coo_rank1(int m, int nblk, const int *dims_in, const double *b, long nnz, const int *con,
+                             const int *blk, const int *row, const int *col, const double *val, int nterm,
+                             const int *tcon, const int *tblk, const double *tsigma, const double *tvec,
+                             HostProblem &hp, std::string &err) {
     // same entry semantics as the file reader (1-based blocks/rows/cols, con 0 = F0)
     std::vector<int> dims(dims_in, dims_in + nblk);
     for (int k = 0; k < nblk - 1; ++k)
@@ -501,7 +608,60 @@ bool build_problem_coo(int m, int nblk, const int *dims_in, const double *b, lon
         if (ic == 0) v = -v;
         raw.push_back({ib, ic, ij, ii, v});
     }
-    return build_problem(m, K, dims, nLp, lpEntries, raw, hp, err);
+    if (nterm <= 0) return build_problem(m, K, dims, nLp, lpEntries, raw, hp, err);
+    if (!tcon || !tblk || !tsigma || !tvec) { err = "rank-one terms: null argument"; return false; }
+    // the (block, constraint) pairs with explicit entries: a term may not share one
+    std::vector<std::pair<int, int>> have;
+    have.reserve(raw.size());
+    for (const RawEntry &e : raw) have.push_back({e.cone, e.con});
+    std::sort(have.begin(), have.end());
+    have.erase(std::unique(have.begin(), have.end()), have.end());
+    std::vector<Rank1Term> terms;
+    char msg[200];
+    const double *a = tvec;
+    for (int t = 0; t < nterm; ++t) {
+        const int ic = tcon[t], ib = tblk[t] - 1;
+        if (ic == 0) {
+            snprintf(msg, sizeof(msg), "rank-one term %d: on constraint 0 (a rank-one objective is not supported)", t);
+            err = msg;
+            return false;
+        }
+        if (ib == K && nLp > 0) {
+            snprintf(msg, sizeof(msg), "rank-one term %d: in the LP block", t);
+            err = msg;
+            return false;
+        }
+        if (ic < 0 || ic > m || ib < 0 || ib >= K) {
+            snprintf(msg, sizeof(msg), "rank-one term %d: constraint %d / block %d out of range", t, ic, ib + 1);
+            err = msg;
+            return false;
+        }
+        if (std::binary_search(have.begin(), have.end(), std::make_pair(ib, ic))) {
+            snprintf(msg, sizeof(msg), "rank-one term %d: constraint %d also has explicit entries in block %d", t, ic,
+                     ib + 1);
+            err = msg;
+            return false;
+        }
+        const int n = dims[ib];
+        long z = 0;
+        for (int j = 0; j < n; ++j) z += a[j] != 0.0 ? 1 : 0;
+        // the reference's rule on the expansion: z (z + 1) / 2 entries, dense iff more than 10 %
+        // of the lower triangle (strictly)
+        if ((double)(z * (z + 1) / 2) > 0.1 * (double)((long)n * (n + 1) / 2)) {
+            Rank1Term rt;
+            rt.con = ic; rt.cone = ib; rt.sigma = tsigma[t];
+            rt.a.assign(a, a + n);
+            terms.push_back(std::move(rt));
+        } else {
+            for (int j = 0; j < n; ++j)
+                for (int k2 = 0; k2 <= j; ++k2) {
+                    const double v = tsigma[t] * a[j] * a[k2];
+                    if (a[j] != 0.0 && a[k2] != 0.0 && std::fabs(v) >= 1e-12) raw.push_back({ib, ic, j, k2, v});
+                }
+        }
+        a += n;
+    }
+    return build_problem(m, K, dims, nLp, lpEntries, raw, hp, err, true, &terms);
 }
 
 bool shard_problem(const HostProblem &g, int world, int rank, HostProblem &out, ShardPlan &plan, std::string &err) {
@@ -520,6 +680,12 @@ bool shard_problem(const HostProblem &g, int world, int rank, HostProblem &out, 
         if (g.cones[k].dense_a) {
             // the stack's products A_i X need every row of X and of A_i: not split by rows
             err = "sharded solve: a cone on the dense constraint-matrix path is not supported (LRS_DENSE_A=0 keeps it on the slots)";
+            return false;
+        }
+    for (int k = 0; k < K; ++k)
+        if (g.cones[k].r1_path) {
+            // V^T X sums over every row of the cone: not split by rows
+            err = "sharded solve: a cone with a rank-one factor of dense constraint coefficients is not supported (LRS_RANK1_A=0 keeps them unfactored)";
             return false;
         }
     for (int k = 0; k < K; ++k)
@@ -1181,7 +1347,7 @@ bool upload_problem(const HostProblem &hp, DevProblem &dp, std::string &err) {
             !dput(&d.adj_col, c.adj_col, err) || !dput(&d.adj_slot, adj_slot_g, err))
             return false;
         // (a constant objective, const_c, is dense_c too: its rank-one form is the kernel's cconst 2)
-        if (c.own1 < 0 && c.n <= kScMaxN && (!c.dense_c || c.const_c) && !c.dense_a &&
+        if (c.own1 < 0 && c.n <= kScMaxN && (!c.dense_c || c.const_c) && !c.dense_a && !c.r1_path &&
             !upload_small_cg(c, hp.m, d, err))
             return false;
         if (c.n >= kNX && (long)c.adj_col.size() >= (long)kTileMinDeg * c.n) {
@@ -1345,11 +1511,17 @@ bool upload_problem(const HostProblem &hp, DevProblem &dp, std::string &err) {
             dp.ndense++;
         }
         if (c.dense_a) {   // dense-A path: the coefficient stack and its constraints
-            d.kd = (int)c.dense_con.size();
-            d.dA_con_h = c.dense_con;
-            if (!dput(&d.dA, c.dA, err) || !dput(&d.dA_con, c.dense_con, err)) return false;
-            dp.ndensea++;
+            d.kd = (int)c.stack_con.size();
+            d.dA_con_h = c.stack_con;
+            if (!dput(&d.dA, c.dA, err) || !dput(&d.dA_con, c.stack_con, err)) return false;
         }
+        if (c.r1_path) {   // rank-one factor: V, the signs and the terms' constraints
+            d.rp = c.rp;
+            d.rldp = c.rldp;
+            if (!dput(&d.rV, c.rV, err) || !dput(&d.r_sigma, c.r_sigma, err) || !dput(&d.r_con, c.r_con, err))
+                return false;
+        }
+        if (c.dense_a || c.r1_path) dp.ndensea++;
     }
     return true;
 }
@@ -1364,7 +1536,7 @@ void free_problem(DevProblem &dp) {
         f(c.sb_blk); f(c.sb_tp); f(c.sb_rp); f(c.sb_ent); f(c.sa_S); f(c.sx_slot);
         f(c.cg_cadj_ptr); f(c.cg_cadj); f(c.cg_cl_con); f(c.cg_cl_ptr); f(c.cg_ce); f(c.cg_sp); f(c.cg_sj);
         f(c.cg_cc_ptr); f(c.cg_cc); f(c.cg_ce_w); f(c.cg_sa); f(c.cobj_slot); f(c.lp_slot); f(c.lp_nrm2);
-        f(c.dA); f(c.dA_con); }
+        f(c.dA); f(c.dA_con); f(c.rV); f(c.r_sigma); f(c.r_con); }
     if (dp.has_merged) {
         f(dp.merged.adj_ptr); f(dp.merged.adj_low); f(dp.merged.adj_col); f(dp.merged.adj_slot);
         f(dp.merged.dra); f(dp.merged.drb);

@@ -45,6 +45,22 @@ struct HostCone {
     bool dense_a = false;
     std::vector<int> dense_con;
     std::vector<double> dA;
+    // stack_con: the constraints of the stack's matrices, ascending (dense_con without the
+    // factored ones below).
+    std::vector<int> stack_con;
+    // rank-one dense coefficients A_i = sigma a a^T (policy below): r1_con / r1_sig the 0-based
+    // constraints the detection accepted and their signs (whichever path the cone takes).  A cone
+    // on the factor path (r1_path) keeps them -- and the terms lrs_load_coo_rank1 passes -- out of
+    // the pattern, of `ent` and of the stack, as the factor rV: n x rldp row-major, row i holding
+    // a_1[i] .. a_rp[i], padding 0 (rldp: rp rounded up to 16, one MFMA tile); term t has sign
+    // r_sigma[t] and belongs to constraint r_con[t] (0-based, ascending; a constraint may own
+    // several consecutive terms, the detection yields one).
+    std::vector<int> r1_con;
+    std::vector<double> r1_sig;
+    bool r1_path = false;
+    int rp = 0, rldp = 0;
+    std::vector<double> rV, r_sigma;
+    std::vector<int> r_con;
     // the LP block (last block of negative size in SDPA) as the diagonal cone at rank 1
     // (build_problem): its columns are the rows, every slot (j, j)
     bool lp = false;
@@ -60,8 +76,24 @@ constexpr int kDenseCMinN = 1024;
 // at least kDenseAMinEntries lower-triangle entries together.  Measured (scripts/densea_probe.py,
 // k_d = 16 at r = 32): the slot path's trip costs ~1.6 ns per such entry, the
 // dense path's ~0.4 ms of host-driven launches plus the stack passes -- 1.49x the slot path at
-// n = 250 (326 304 entries), 0.31x at n = 120 (75 504).
+// n = 250 (326 304 entries), 0.31x at n = 120 (75 504).  The same threshold holds for cones whose
+// dense coefficients are rank one (scripts/rank1_probe.py): the factor's trip is
+// ~0.35 ms at every n, the slots' ~1.14 ns per entry, equal at ~300 000 entries -- not lowered.
 constexpr long kDenseAMinEntries = 320000;
+// Rank-one policy: every coefficient the rule above types dense is tested for A = sigma a a^T:
+// pv the index of the largest |A_pp| (0: not rank one), sigma = sign(A_pvpv), a = A[:, pv] /
+// sqrt|A_pvpv|, accepted iff max_jk |A_jk - sigma a_j a_k| <= kRank1Tol max|A| (the rule's own
+// rounding residual stays below 4e-16; 1e-13 is four orders under the 1e-9 trip bars and still
+// rejects a a^T + 1e-6 b b^T or one entry moved by 1e-9).  LRS_RANK1_A=0: no detection; =1: every
+// cone with an accepted coefficient factors them (its other dense coefficients follow LRS_DENSE_A);
+// unset: the cones LRS_DENSE_A / kDenseAMinEntries select factor theirs, the rest go to the stack.
+constexpr double kRank1Tol = 1e-13;
+// one factored term of lrs_load_coo_rank1: sigma a a^T on (constraint con >= 1, SDP cone)
+struct Rank1Term {
+    int con = 0, cone = 0;
+    double sigma = 1.0;
+    std::vector<double> a;
+};
 // Constant-objective policy: a block whose C has all n (n + 1) / 2 entries equal can take the
 // rank-one products (any n >= 2).  LRS_CONST_C=1 every such block, =0 none; unset: only when
 // the whole problem fits the single-workgroup inner loop at every rank the solve can reach
@@ -97,6 +129,14 @@ bool read_sdpa(const std::string &path, HostProblem &hp, std::string &err);
 bool build_problem_coo(int m, int nblk, const int *dims, const double *b, long nnz, const int *con,
                        const int *blk, const int *row, const int *col, const double *val, HostProblem &hp,
                        std::string &err);
+// The same plus nterm rank-one terms tsigma[t] a_t a_t^T on (constraint tcon[t], block tblk[t]),
+// the vectors concatenated in tvec (each of its block's length).  A term whose expansion the
+// reference's rule types sparse (z nonzeros, z (z + 1) / 2 <= 0.1 T) is expanded into entries;
+// every other one is factored (never expanded).
+bool build_problem_coo_rank1(int m, int nblk, const int *dims, const double *b, long nnz, const int *con,
+                             const int *blk, const int *row, const int *col, const double *val, int nterm,
+                             const int *tcon, const int *tblk, const double *tsigma, const double *tvec,
+                             HostProblem &hp, std::string &err);
 
 // Sharded solve: the rows of every cone split into `world` contiguous
 // blocks balanced by adjacency entries (a multi-block problem: each block split alike).  Shard `rank` owns rows

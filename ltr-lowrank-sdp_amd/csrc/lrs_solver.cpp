@@ -569,7 +569,8 @@ static void free_work(lrs_ctx *c) {
     double *ptrs[] = {W.R, W.D, W.G[0], W.G[1], W.ls[0], W.ly[0], W.ls[1], W.ly[1], W.U, W.V, W.X, W.cg_r,
                       W.cg_p, W.cg_Q, W.cg_b, W.M2, W.uvt0, W.uvt1, W.uvt2, W.S, W.lam, W.cvs, W.q1, W.q2,
                       W.M1, W.wtmp, W.cvc, W.part, W.partB, W.partC, W.ctrl, W.lsres, W.par, W.gram, W.rec, W.R2,
-                      W.cgc, W.tot, W.gl, W.CR, W.CD, W.GP, W.CGK, W.uvp, W.lpw, W.dT, W.dSd, W.dpart};
+                      W.cgc, W.tot, W.gl, W.CR, W.CD, W.GP, W.CGK, W.uvp, W.lpw, W.dT, W.dSd, W.dpart, W.rTx, W.rTz, W.rTy,
+                      W.rpart};
     for (double *p : ptrs)
         if (p) (void)hipFree(p);
     for (double *q : c->ring_s) if (q) (void)hipFree(q);
@@ -661,6 +662,14 @@ static int alloc_work(lrs_ctx *c, const std::vector<int> &ranks) {
             nP = std::max(nP, 2L * dc.kd * dcon_tiles(dc));
         }
         if (A(&W.dT, nT) || A(&W.dSd, nS) || A(&W.dpart, nP)) return -1;
+        // rank-one factors: the three skinny products V^T X and k_r1_vtx's chunk partials
+        long nR = 0, nRp = 1;
+        for (const DevCone &dc : P.cones) {
+            if (!dc.rp) continue;
+            nR = std::max(nR, (long)dc.rldp * dc.ld);
+            nRp = std::max(nRp, r1_part_len(dc, dc.r));
+        }
+        if (nR && (A(&W.rTx, nR) || A(&W.rTz, nR) || A(&W.rTy, nR) || A(&W.rpart, nRp))) return -1;
     }
     {   // k_cgemm2's split-K slabs for the large dense cones
         bool big = false;
@@ -800,6 +809,23 @@ static int dense_a_adj(lrs_ctx *c, int k, const double *w, const double *X, doub
     OPC(launch_dcon_comb(c->dp, k, w, c->W.dT, scale, 1.0, out, nullptr, nullptr, nullptr, c->st));
     return 0;
 }
+// Rank-one factor of cone k (DevCone::rV): out[i] += scale sigma_t <(V^T X)_t,
+// (V^T Y)_t> (Y null: X) for the cone's terms t of constraint i, and outb[i] too when given; one
+// pass over V (k_r1_vtx), then the terms in index order (k_r1_vals)
+static int r1_vals(lrs_ctx *c, int k, const double *X, const double *Y, double scale, double *out, double *outb) {
+    const DevCone &dc = c->dp.cones[k];
+    DevWork &W = c->W;
+    OPC(launch_r1_vtx(dc, dc.r, dc.ld, X + dc.foff, Y ? Y + dc.foff : nullptr, W.rTx, W.rTz, W.rpart, c->st));
+    OPC(launch_r1_vals(dc, dc.r, dc.ld, W.rTx, Y ? W.rTz : nullptr, 0.0, nullptr, scale, out, outb, 1, c->st));
+    return 0;
+}
+// out rows of cone k += scale V diag(w sigma) (V^T X); the product T = V^T X is left in `T`
+static int r1_adj(lrs_ctx *c, int k, const double *w, const double *X, double scale, double *out, double *T) {
+    const DevCone &dc = c->dp.cones[k];
+    OPC(launch_r1_vtx(dc, dc.r, dc.ld, X + dc.foff, nullptr, T, nullptr, c->W.rpart, c->st));
+    OPC(launch_r1_apply(dc, dc.r, dc.ld, w, T, scale, 1.0, out + dc.foff, nullptr, nullptr, nullptr, c->st));
+    return 0;
+}
 // A(X X^T) for every cone -> cvc[k], cvs = sum_k, returns pinf (primalInfeasibility)
 // and the objective <C, X X^T> (unscaled), with X given per-cone rows in factor buffer.
 // blam != nullptr: also b^T lambda (tmpfin TF_DOT), read behind the same sync
@@ -849,6 +875,8 @@ READ:
         // dense coefficients: their values into the sum and the cone's own, then the residual anew
         for (int k = 0; k < P.K; ++k)
             if (P.cones[k].kd && dense_a_vals(c, k, X, Y, 1.0, W.cvs, W.cvc + (long)k * P.m)) return -1;
+        for (int k = 0; k < P.K; ++k)   // rank-one factors likewise
+            if (P.cones[k].rp && r1_vals(c, k, X, Y, 1.0, W.cvs, W.cvc + (long)k * P.m)) return -1;
         OPC(launch_resid(P.m, P.b, W.cvs, c->st, P.cmask));
         fin = TF_RESID;
     }
@@ -887,7 +915,7 @@ static int op_grad(lrs_ctx *c, double rho, double *lag) {
     // dense objective: C R (the inner loop carries it), G += 2 C R, ||G||^2 anew
     for (int k = 0; k < P.K; ++k) {
         const DevCone &dc = P.cones[k];
-        if (!dc.dense_c && !dc.kd) continue;
+        if (!dc.dense_c && !dc.kd && !dc.rp) continue;
         const long ro = dc.foff + (long)dc.row0 * dc.ld;   // the rows C R covers (sharded: owned)
         double *Gk = W.G[c->gcur] + ro;
         if (dc.dense_c) {
@@ -896,6 +924,8 @@ static int op_grad(lrs_ctx *c, double rho, double *lag) {
         }
         // dense coefficients: G += 2 sum_i M1_i A_i R
         if (dc.kd && dense_a_adj(c, k, W.M1, W.R, 2.0, W.G[c->gcur])) return -1;
+        // rank-one factor: G += 2 V diag(M1 sigma) (V^T R)
+        if (dc.rp && r1_adj(c, k, W.M1, W.R, 2.0, W.G[c->gcur], W.rTx)) return -1;
         if (op_dot(c, (long)dc.nown * dc.ld, Gk, Gk, &v[k])) return -1;
     }
     double tot = 0.0;
@@ -1204,8 +1234,12 @@ static int dual_infeasibility(lrs_ctx *c, double *l1, double *lmin, int *all_con
             OPC(launch_dcon_wsum(c->dp, k, W.wtmp, W.dSd, c->st));
             dk.dSd = W.dSd;
         }
+        // rank-one factor: -sum_t lambda sigma_t a_t (a_t^T x) per product, through the factor
+        // kernels at r = 1 (no n x n matrix is formed)
+        if (dk.rp) { dk.r1w = W.wtmp; dk.r1T = W.rTx; dk.r1part = W.rpart; }
         const int trc = trl_min(c, k, W.S, &lk, &steps, &iters, &conv);
         dk.dSd = nullptr;
+        dk.r1w = nullptr;
         if (trc) return -1;
         c->dinf_steps += steps;
         c->dinf_iters += iters;
@@ -1950,6 +1984,13 @@ static int op_q12_fin(lrs_ctx *c, double *p1h, double *p2h) {
         OPC(launch_dcon_ax(P, k, dc.kd, dc.dA, W.D, W.R, nullptr, W.dpart, c->st));
         OPC(launch_dcon_fin(P, k, W.dpart, 1.0, W.q2, 2.0, W.q1, nullptr, 1, c->st));
     }
+    // rank-one factors: q2_i = sigma <V^T D, V^T D>_t, q1_i = 2 sigma <V^T D, V^T R>_t, V read once
+    for (int k = 0; k < P.K; ++k) {
+        const DevCone &dc = P.cones[k];
+        if (!dc.rp) continue;
+        OPC(launch_r1_vtx(dc, dc.r, dc.ld, W.D + dc.foff, W.R + dc.foff, W.rTx, W.rTz, W.rpart, c->st));
+        OPC(launch_r1_vals(dc, dc.r, dc.ld, W.rTx, W.rTz, 1.0, W.q2, 2.0, W.q1, nullptr, 1, c->st));
+    }
     double *fin = c->s_fin;   // this context's finals (the line search reads them)
     double h[64] = {0};
     h[0] = a; h[1] = b;
@@ -2267,14 +2308,26 @@ static int cg_solve(lrs_ctx *c, int k, const double *Y, double *X, const double 
         OPC(launch_auv_con(P, k, 0, x, Y, 1.0, 0, W.wtmp, nullptr, nullptr, c->st, guard));
         // dense coefficients: <A_i, sym(x Y^T)> = <x, T_i> with the half-step's T_i = A_i Y (W.dT)
         if (d.kd) OPC(launch_dcon_dots(P, k, W.dT, x, W.wtmp, nullptr, 1, c->st));
+        // rank-one factor: sigma <V^T x, V^T Y>_t with the half-step's V^T Y (W.rTy)
+        if (d.rp) {
+            OPC(launch_r1_vtx(d, d.r, d.ld, x + d.foff, nullptr, W.rTx, nullptr, W.rpart, c->st));
+            OPC(launch_r1_vals(d, d.r, d.ld, W.rTx, W.rTy, 0.0, nullptr, 1.0, W.wtmp, nullptr, 1, c->st));
+        }
         OPC(sync_shared(P, W.wtmp, c->st));
         return 0;
     };
     // Q += sum_i wtmp_i T_i over the dense coefficients; `part`: the fused <x, Q> retaken over the
     // whole Q (launch_cg_mv's partials hold the slot part only)
     auto dmv = [&](const double *x, double *part, int *nblk) -> int {
-        if (!d.kd) return 0;
-        OPC(launch_dcon_comb(P, k, W.wtmp, W.dT, 1.0, 1.0, W.cg_Q, part ? x : nullptr, part, part ? nblk : nullptr, c->st));
+        if (!d.kd && !d.rp) return 0;
+        const bool last_d = !d.rp;   // the last term's kernel takes the partials, over the whole Q
+        if (d.kd)
+            OPC(launch_dcon_comb(P, k, W.wtmp, W.dT, 1.0, 1.0, W.cg_Q, part && last_d ? x : nullptr,
+                                 last_d ? part : nullptr, part && last_d ? nblk : nullptr, c->st));
+        // rank-one factor: Q += V diag(wtmp sigma) (V^T Y)
+        if (d.rp)
+            OPC(launch_r1_apply(d, d.r, d.ld, W.wtmp, W.rTy, 1.0, 1.0, W.cg_Q + d.foff, part ? x + d.foff : nullptr, part,
+                                part ? nblk : nullptr, c->st));
         return 0;
     };
     OPC(launch_cg_nrm1(nr, bk, W.part, c->st, &nA));
@@ -2334,6 +2387,8 @@ static int update_var_one(lrs_ctx *c, int k, double *X, const double *Y, double 
     // dense coefficients: + sum_i M1_i A_i Y; the products T_i = A_i Y stay in W.dT for the CG
     // and the refresh (Y is fixed over the half-step: no further pass over the stack)
     if (d.kd && dense_a_adj(c, k, W.M1, Y, 1.0, W.M2)) return -1;
+    // rank-one factor: + V diag(M1 sigma) (V^T Y); V^T Y stays in W.rTy for the CG and the refresh
+    if (d.rp && r1_adj(c, k, W.M1, Y, 1.0, W.M2, W.rTy)) return -1;
     OPC(launch_axpby((long)d.n * d.ld, -1.0 / rho, W.M2 + d.foff, 0.0, W.cg_b + d.foff, c->st));
     if (cg_solve(c, k, Y, X, W.cg_b, tol, maxit)) return -1;
     c->cgIterTotal += c->cgIterCone[k];
@@ -2363,6 +2418,13 @@ static int refresh_cone(lrs_ctx *c, int k, const double *solved = nullptr) {   /
         if (solved) OPC(launch_dcon_dots(P, k, W.dT, solved, cv, W.cvs, 1, c->st));
         else if (dense_a_vals(c, k, W.U, W.V, 1.0, cv, W.cvs)) return -1;
     }
+    if (P.cones[k].rp) {   // rank-one factor likewise: V^T of the solved side against W.rTy
+        const DevCone &d = P.cones[k];
+        if (solved) {
+            OPC(launch_r1_vtx(d, d.r, d.ld, solved + d.foff, nullptr, W.rTx, nullptr, W.rpart, c->st));
+            OPC(launch_r1_vals(d, d.r, d.ld, W.rTx, W.rTy, 0.0, nullptr, 1.0, cv, W.cvs, 1, c->st));
+        } else if (r1_vals(c, k, W.U, W.V, 1.0, cv, W.cvs)) return -1;
+    }
     return 0;
 }
 
@@ -2374,6 +2436,7 @@ static int admm_init_constr(lrs_ctx *c) {
     for (int k = 0; k < P.K; ++k) {
         OPC(launch_auv_con(P, k, 0, c->W.U, c->W.V, 1.0, 0, c->W.cvc + (long)k * P.m, nullptr, nullptr, c->st));
         if (P.cones[k].kd && dense_a_vals(c, k, c->W.U, c->W.V, 1.0, c->W.cvc + (long)k * P.m, nullptr)) return -1;
+        if (P.cones[k].rp && r1_vals(c, k, c->W.U, c->W.V, 1.0, c->W.cvc + (long)k * P.m, nullptr)) return -1;
         OPC(sync_shared(P, c->W.cvc + (long)k * P.m, c->st));
         OPC(launch_axpby(P.m, 1.0, c->W.cvc + (long)k * P.m, 1.0, c->W.cvs, c->st));
     }
@@ -2904,6 +2967,33 @@ int lrs_load_coo(lrs_ctx *c, int m, int nblk, const int *dims, const double *b, 
     return 0;
 }
 
+// lrs_load_coo plus nterm rank-one terms tsigma[t] a_t a_t^T (build_problem_coo_rank1: a term the
+// reference's rule types sparse is expanded into entries, every other one goes to the factor)
+int lrs_load_coo_rank1(lrs_ctx *c, int m, int nblk, const int *dims, const double *b, long nnz, const int *con,
+                       const int *blk, const int *row, const int *col, const double *val, int nterm, const int *tcon,
+                       const int *tblk, const double *tsigma, const double *tvec) {
+    LRS_NEED_CTX(c);
+    LRS_NEED_ARG(dims);
+    if (m > 0) LRS_NEED_ARG(b);
+    if (nnz > 0 && (!con || !blk || !row || !col || !val)) { set_err("lrs_load_coo_rank1: null entry array"); return -1; }
+    if (nterm > 0 && (!tcon || !tblk || !tsigma || !tvec)) { set_err("lrs_load_coo_rank1: null term array"); return -1; }
+    std::string err;
+    HostProblem hp;
+    if (!build_problem_coo_rank1(m, nblk, dims, b, nnz, con, blk, row, col, val, nterm, tcon, tblk, tsigma, tvec, hp,
+                                 err)) {
+        set_err("load_coo_rank1: %s", err.c_str());
+        return -1;
+    }
+    free_work(c);
+    if (c->loaded) free_problem(c->dp);
+    c->hp = std::move(hp);
+    if (!upload_problem(c->hp, c->dp, err)) { set_err("upload: %s", err.c_str()); return -1; }
+    c->loaded = true;
+    c->path = "<memory>";
+    c->cgIterCone.assign(c->hp.K, 0);
+    return 0;
+}
+
 int lrs_auut_bytes(lrs_ctx *c, double *bytes) {
     LRS_NEED_STATE(c);
     LRS_NEED_ARG(bytes);
@@ -3234,6 +3324,8 @@ int lrs_op_adjoint(lrs_ctx *c, const double *y, int which, double *out, double s
     }
     for (int k = 0; k < P.K; ++k)   // dense coefficients: + scale sum_i y_i A_i X
         if (P.cones[k].kd && dense_a_adj(c, k, W.M1, X, scale, W.X)) return -1;
+    for (int k = 0; k < P.K; ++k)   // rank-one factors: + scale V diag(y sigma) (V^T X)
+        if (P.cones[k].rp && r1_adj(c, k, W.M1, X, scale, W.X, W.rTx)) return -1;
     return factor_fetch(c, W.X, out);
 }
 
@@ -3732,7 +3824,7 @@ int lrs_dense_a_info(lrs_ctx *c, int cone, int *n_dense, int *on_dense_path, lon
     const HostCone &h = c->hp.cones[cone];
     if (n_dense) *n_dense = (int)h.dense_con.size();
     if (on_dense_path) *on_dense_path = h.dense_a ? 1 : 0;
-    if (stack_bytes) *stack_bytes = h.dense_a ? (long)(h.dense_con.size() * (size_t)h.n * h.n * sizeof(double)) : 0;
+    if (stack_bytes) *stack_bytes = h.dense_a ? (long)(h.stack_con.size() * (size_t)h.n * h.n * sizeof(double)) : 0;
     return 0;
 }
 
@@ -3773,6 +3865,61 @@ int lrs_dense_a_plan(const char *path, int cone, int *n_dense, int *on_dense_pat
     if (n_dense) *n_dense = (int)h.dense_con.size();
     if (on_dense_path) *on_dense_path = h.dense_a ? 1 : 0;
     for (int j = 0; cons && j < cap && j < (int)h.dense_con.size(); ++j) cons[j] = h.dense_con[j];
+    return 0;
+}
+
+// Rank-one dense coefficients of a cone (lrs_problem.h policy) and whether it keeps a factor
+int lrs_rank1_info(lrs_ctx *c, int cone, int *n_rank1, int *on_factor_path, long *factor_bytes) {
+    LRS_NEED_LOADED(c);
+    if (cone < 0 || cone >= c->dp.K) { set_err("rank1_info: cone %d of %d", cone, c->dp.K); return -1; }
+    const HostCone &h = c->hp.cones[cone];
+    if (n_rank1) *n_rank1 = (int)h.r1_con.size();
+    if (on_factor_path) *on_factor_path = h.r1_path ? 1 : 0;
+    if (factor_bytes) *factor_bytes = h.r1_path ? (long)(h.rV.size() * sizeof(double)) : 0;
+    return 0;
+}
+
+// k_r1_vtx on R (finish included): reps launches back to back; bytes = n (ldp + ld) 8
+int lrs_time_rank1(lrs_ctx *c, int cone, int reps, double *avg_ms, double *bytes) {
+    if (!c || !avg_ms) { set_err("time_rank1: null argument"); return -1; }
+    bind(c);
+    if (!c->walloc || cone < 0 || cone >= c->dp.K || !c->dp.cones[cone].rp) {
+        set_err("time_rank1: cone %d has no rank-one factor (or no ranks set)", cone);
+        return -1;
+    }
+    const DevCone &dc = c->dp.cones[cone];
+    hipEvent_t e0, e1;
+    HIPC(hipEventCreate(&e0));
+    HIPC(hipEventCreate(&e1));
+    OPC(launch_r1_vtx(dc, dc.r, dc.ld, c->W.R + dc.foff, nullptr, c->W.rTx, nullptr, c->W.rpart, c->st));
+    HIPC(hipEventRecord(e0, c->st));
+    for (int q = 0; q < reps; ++q)
+        OPC(launch_r1_vtx(dc, dc.r, dc.ld, c->W.R + dc.foff, nullptr, c->W.rTx, nullptr, c->W.rpart, c->st));
+    HIPC(hipEventRecord(e1, c->st));
+    HIPC(hipEventSynchronize(e1));
+    float ms = 0;
+    HIPC(hipEventElapsedTime(&ms, e0, e1));
+    *avg_ms = ms / std::max(1, reps);
+    if (bytes) *bytes = 8.0 * dc.n * ((double)dc.rldp + dc.ld);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return 0;
+}
+
+// Host-only: the rank-one dense coefficients of the instance at `path`, per cone
+int lrs_rank1_plan(const char *path, int cone, int *n_rank1, int *on_factor_path, int *cons, double *sigma, int cap) {
+    if (!path) { set_err("null argument"); return -1; }
+    HostProblem g;
+    std::string err;
+    if (!read_sdpa(path, g, err)) { set_err("read_sdpa: %s", err.c_str()); return -1; }
+    if (cone < 0 || cone >= g.K) { set_err("rank1_plan: cone %d of %d", cone, g.K); return -1; }
+    const HostCone &h = g.cones[cone];
+    if (n_rank1) *n_rank1 = (int)h.r1_con.size();
+    if (on_factor_path) *on_factor_path = h.r1_path ? 1 : 0;
+    for (int j = 0; j < cap && j < (int)h.r1_con.size(); ++j) {
+        if (cons) cons[j] = h.r1_con[j];
+        if (sigma) sigma[j] = h.r1_sig[j];
+    }
     return 0;
 }
 

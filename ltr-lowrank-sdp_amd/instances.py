@@ -37,6 +37,8 @@ __all__ = [
     "maxcut_lp",
     "dense_constraints_problem",
     "dense_constraints",
+    "rank_one_constraints_problem",
+    "rank_one_constraints",
 ]
 
 
@@ -307,6 +309,79 @@ def dense_constraints_problem(dims, m_sparse, k, fills, cross, seed):
         b.append(bi)
         con0 += 1
     return con0 - 1, dims, np.array(b), entries
+
+
+def rank_one_constraints_problem(dims, m_sparse, k, n_terms, n_full, neg, hole, hole_frac, cross, boundary, seed,
+                                 scale=1.0, expand=True):
+    """Rank-one dense constraint matrices in memory: ((m, dims, b, entries), terms).  C = I on
+    every block and m_sparse[b] sparse constraints of k entries per block, as
+    dense_constraints_problem.  Block 1 then gets n_full constraints with all T = n (n + 1) / 2
+    lower-triangle positions N(0,1) (full rank), and n_terms constraints A = sigma a a^T with a ~
+    scale N(0,1)^n: the term of index `neg` (None: none) has sigma = -1, the term of index `hole` has a
+    fraction hole_frac of a's entries set to zero, the term of index `cross` also has five
+    random entries in block 2.  With `boundary`, one more term follows whose vector has the
+    largest number z of nonzeros with z (z + 1) / 2 <= floor(0.1 T): the reference's strict 10 %
+    rule keeps it sparse.  b_i = tr(A_i) (= sigma ||a||^2 for a term), so X = I is feasible.
+    terms: [(constraint, block, sigma, a)], 1-based, in constraint order; `entries` holds their
+    expansion sigma a_j a_k (expand=False: leaves it out, for Solver(coo=...) with "terms")."""
+    rng = np.random.default_rng(seed)
+    dims = [int(d) for d in dims]
+    entries, b, terms = [], [], []
+    for blk, n in enumerate(dims, start=1):
+        d = np.arange(1, n + 1)
+        entries.append((np.zeros(n, dtype=np.int64), blk, d, d, -np.ones(n)))
+    con0 = 1
+    for blk, (n, ms) in enumerate(zip(dims, m_sparse), start=1):
+        ii = rng.integers(0, n, size=(ms, k))
+        jj = rng.integers(0, n, size=(ms, k))
+        lo, hi = np.minimum(ii, jj), np.maximum(ii, jj)
+        v = rng.standard_normal((ms, k))
+        b += np.where(lo == hi, v, 0.0).sum(axis=1).tolist()
+        entries.append((np.repeat(np.arange(con0, con0 + ms), k), blk, lo.ravel() + 1, hi.ravel() + 1, v.ravel()))
+        con0 += ms
+    n = dims[0]
+    iu, ju = np.triu_indices(n)
+    T = iu.size
+    for _ in range(n_full):
+        v = rng.standard_normal(T)
+        entries.append((np.full(T, con0, dtype=np.int64), 1, iu + 1, ju + 1, v))
+        b.append(float(v[iu == ju].sum()))
+        con0 += 1
+    zb = int((np.sqrt(8.0 * np.floor(0.1 * T) + 1.0) - 1.0) / 2.0)
+    while (zb + 1) * (zb + 2) // 2 <= int(np.floor(0.1 * T)):
+        zb += 1
+    for t in range(n_terms + (1 if boundary else 0)):
+        a = scale * rng.standard_normal(n)
+        sigma = -1.0 if (neg is not None and t == neg) else 1.0
+        if t == n_terms:
+            a[np.sort(rng.choice(n, size=n - zb, replace=False))] = 0.0
+        elif hole is not None and t == hole:
+            a[np.sort(rng.choice(n, size=int(round(hole_frac * n)), replace=False))] = 0.0
+        bi = sigma * float(a @ a)
+        terms.append((con0, 1, sigma, a))
+        if expand:
+            v = sigma * a[iu] * a[ju]
+            nz = v != 0.0
+            entries.append((np.full(int(nz.sum()), con0, dtype=np.int64), 1, iu[nz] + 1, ju[nz] + 1, v[nz]))
+        if cross is not None and t == cross:
+            n2 = dims[1]
+            i2 = rng.integers(0, n2, size=5)
+            j2 = rng.integers(0, n2, size=5)
+            lo, hi = np.minimum(i2, j2), np.maximum(i2, j2)
+            v2 = rng.standard_normal(5)
+            bi += float(v2[lo == hi].sum())
+            entries.append((np.full(5, con0, dtype=np.int64), 2, lo + 1, hi + 1, v2))
+        b.append(bi)
+        con0 += 1
+    return (con0 - 1, dims, np.array(b), entries), terms
+
+
+def rank_one_constraints(path, dims, m_sparse, k, n_terms, n_full, neg, hole, hole_frac, cross, boundary, seed,
+                         scale=1.0):
+    """rank_one_constraints_problem written as a .dat-s file (terms expanded); returns (path, terms)."""
+    prob, terms = rank_one_constraints_problem(dims, m_sparse, k, n_terms, n_full, neg, hole, hole_frac, cross,
+                                               boundary, seed, scale)
+    return write_sdpa(path, *prob), terms
 
 
 def dense_constraints(path, dims, m_sparse, k, fills, cross, seed):

@@ -133,7 +133,12 @@ def load_library(path=None):
         "lrs_dense_a_info": (C.c_int, [vp, C.c_int, ip, ip, C.POINTER(C.c_long)]),
         "lrs_time_dense_a": (C.c_int, [vp, C.c_int, C.c_int, dp]),
         "lrs_dense_a_plan": (C.c_int, [C.c_char_p, C.c_int, ip, ip, ip, C.c_int]),
+        "lrs_rank1_info": (C.c_int, [vp, C.c_int, ip, ip, C.POINTER(C.c_long)]),
+        "lrs_rank1_plan": (C.c_int, [C.c_char_p, C.c_int, ip, ip, ip, dp, C.c_int]),
+        "lrs_time_rank1": (C.c_int, [vp, C.c_int, C.c_int, dp, dp]),
         "lrs_load_coo": (C.c_int, [vp, C.c_int, C.c_int, ip, dp, C.c_long, ip, ip, ip, ip, dp]),
+        "lrs_load_coo_rank1": (C.c_int, [vp, C.c_int, C.c_int, ip, dp, C.c_long, ip, ip, ip, ip, dp, C.c_int, ip, ip,
+                                         dp, dp]),
         "lrs_debug_phase_times": (C.c_int, [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
         "lrs_comm_unique_id": (C.c_int, [C.c_char_p]),
         "lrs_shard_rccl": (C.c_int, [vp, C.c_int, C.c_int, C.c_char_p]),
@@ -222,9 +227,24 @@ class Solver:
             a = {k: coo[k] for k in ("dims", "b", "con", "blk", "row", "col", "val")}
             ip_ = lambda x: x.ctypes.data_as(C.POINTER(C.c_int))
             dp_ = lambda x: x.ctypes.data_as(C.POINTER(C.c_double))
-            self._check(self.lib.lrs_load_coo(self.ctx, int(coo["m"]), len(a["dims"]), ip_(a["dims"]), dp_(a["b"]),
-                                              len(a["con"]), ip_(a["con"]), ip_(a["blk"]), ip_(a["row"]),
-                                              ip_(a["col"]), dp_(a["val"])), "load_coo")
+            terms = coo.get("terms")
+            if terms:
+                # rank-one terms (con, blk, sigma, a), 1-based con / blk: sigma a a^T (lrs_load_coo_rank1)
+                tcon = np.ascontiguousarray([tm[0] for tm in terms], dtype=np.int32)
+                tblk = np.ascontiguousarray([tm[1] for tm in terms], dtype=np.int32)
+                tsig = np.ascontiguousarray([tm[2] for tm in terms], dtype=np.float64)
+                for tm in terms:
+                    if not 1 <= int(tm[1]) <= len(a["dims"]) or len(tm[3]) != abs(int(a["dims"][int(tm[1]) - 1])):
+                        raise ValueError("rank-one term: block out of range or vector length differs from the block's")
+                tvec = np.ascontiguousarray(np.concatenate([np.asarray(tm[3], dtype=np.float64) for tm in terms]))
+                self._check(self.lib.lrs_load_coo_rank1(self.ctx, int(coo["m"]), len(a["dims"]), ip_(a["dims"]),
+                                                        dp_(a["b"]), len(a["con"]), ip_(a["con"]), ip_(a["blk"]),
+                                                        ip_(a["row"]), ip_(a["col"]), dp_(a["val"]), len(terms),
+                                                        ip_(tcon), ip_(tblk), dp_(tsig), dp_(tvec)), "load_coo_rank1")
+            else:
+                self._check(self.lib.lrs_load_coo(self.ctx, int(coo["m"]), len(a["dims"]), ip_(a["dims"]), dp_(a["b"]),
+                                                  len(a["con"]), ip_(a["con"]), ip_(a["blk"]), ip_(a["row"]),
+                                                  ip_(a["col"]), dp_(a["val"])), "load_coo")
             t.value = _time.perf_counter() - t0
         else:
             self._check(self.lib.lrs_load_sdpa(self.ctx, str(path).encode(), C.byref(t)), "load_sdpa")
@@ -606,6 +626,20 @@ class Solver:
         self._check(self.lib.lrs_time_dense_a(self.ctx, cone, reps, C.byref(t)), "time_dense_a")
         return t.value
 
+    def rank1_info(self, cone=0):
+        """(rank-one dense coefficients of `cone`, whether it keeps a factor, the factor's bytes)
+        (lrs_rank1_info)."""
+        n, on, nb = C.c_int(), C.c_int(), C.c_long()
+        self._check(self.lib.lrs_rank1_info(self.ctx, cone, C.byref(n), C.byref(on), C.byref(nb)), "rank1_info")
+        return n.value, bool(on.value), nb.value
+
+    def time_rank1(self, cone=0, reps=10):
+        """(ms per V^T R launch of `cone`'s rank-one factor, finish included; that launch's
+        algorithmic bytes) (lrs_time_rank1)."""
+        t, b = C.c_double(), C.c_double()
+        self._check(self.lib.lrs_time_rank1(self.ctx, cone, reps, C.byref(t), C.byref(b)), "time_rank1")
+        return t.value, b.value
+
     def mfma_f64_peak(self):
         """Measured FP64 matrix-core TFLOP/s of this device (lrs_mfma_f64_peak)."""
         t = C.c_double()
@@ -638,6 +672,21 @@ def dense_a_plan(path, cone=0):
                             cons.ctypes.data_as(C.POINTER(C.c_int)), n.value) != 0:
         raise RuntimeError(lib.lrs_last_error().decode())
     return cons[:n.value].tolist(), bool(on.value)
+
+
+def rank1_plan(path, cone=0):
+    """Host-only detection of the rank-one dense coefficients of `cone` (lrs_rank1_plan; no device
+    needed): (0-based constraint indices, their signs sigma, whether the cone keeps a factor)."""
+    lib = load_library()
+    n, on = C.c_int(), C.c_int()
+    if lib.lrs_rank1_plan(str(path).encode(), cone, C.byref(n), C.byref(on), None, None, 0) != 0:
+        raise RuntimeError(lib.lrs_last_error().decode())
+    cons = np.zeros(max(1, n.value), dtype=np.int32)
+    sig = np.zeros(max(1, n.value), dtype=np.float64)
+    if lib.lrs_rank1_plan(str(path).encode(), cone, C.byref(n), C.byref(on), cons.ctypes.data_as(C.POINTER(C.c_int)),
+                          sig.ctypes.data_as(C.POINTER(C.c_double)), n.value) != 0:
+        raise RuntimeError(lib.lrs_last_error().decode())
+    return cons[:n.value].tolist(), sig[:n.value].tolist(), bool(on.value)
 
 
 def shard_plan(path, world, rank):
