@@ -231,6 +231,11 @@ int lrs_set_kernel_path(lrs_ctx *ctx, int path);
 /* The path the last enqueued ALM inner iteration of this context took (0 latency-regime
  * kernels, 1 general row kernels; -1 none enqueued yet). */
 int lrs_get_kernel_path(lrs_ctx *ctx, int *used);
+/* *used = 1 when every launch of the last enqueued ALM inner iteration was the latency kernels'
+ * PLAIN instantiation (path 0 on cones whose slots carry at most one constraint entry and at most
+ * one local constraint, without dense-row slices and without a dense objective), else 0.  The
+ * environment variable LRS_LAT_PLAIN=0 selects the general instantiation (same results). */
+int lrs_lat_plain_used(lrs_ctx *ctx, int *used);
 
 /* Standalone A(UU^T) on R (the constraint-entry kernel k_auv_con, all cones): reps
  * launches back to back between two HIP events, average ms per launch; and its

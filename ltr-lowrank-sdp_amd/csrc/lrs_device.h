@@ -101,6 +101,9 @@ struct DevCone {
     int row0 = 0, nown = 0;
     long foff = 0;      // offset (doubles) of this cone in the factor buffer
     int slot_off = 0, P = 0;
+    // every slot has at most one constraint entry and at most one local constraint (slot1.y,
+    // loc1.y never -2): the latency kernels' PLAIN instantiations apply
+    bool plain = false;
     int *adj_ptr = nullptr, *adj_low = nullptr, *adj_col = nullptr, *adj_slot = nullptr;
     long adj_nnz = 0;
     // constraint i of this cone is the single entry (i, i), every i (m = n): k_auv_diag
@@ -227,6 +230,7 @@ struct DevProblem {
     int *slot_g = nullptr;               // [Ptot][2] every slot's (row, col) in the all-cones row space
     mutable int last_path = -1;          // path of the last enqueued iteration (0 lat, 1 general)
     mutable int last_tiles = 0;          // the last enqueued iteration ran stage A / B over the 2-D tiles
+    mutable int last_plain = 0;          // ... every latency launch of it as the PLAIN instantiation
     int m = 0, K = 0;
     int lp_cone = -1;   // the LP block's cone (the last), -1 without one
     long NRpad = 0;     // factor buffer length (doubles)

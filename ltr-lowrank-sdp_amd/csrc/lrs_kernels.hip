@@ -135,6 +135,27 @@ __device__ __forceinline__ double opaque(double x) {
     asm volatile("" : "+v"(x));
     return x;
 }
+// a value (an address, an index) / a uniform int the compiler keeps in vector / scalar registers
+// from here on instead of forming it again from the kernel arguments (a scalar load and its
+// wait) where it is used
+template <typename T>
+__device__ __forceinline__ T held(T x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+template <typename T>
+__device__ __forceinline__ T held_s(T x) {
+    asm volatile("" : "+s"(x));
+    return x;
+}
+// (a pointer into global memory, typed as one: behind the asm its accesses would be flat ones)
+typedef __attribute__((address_space(1))) double gdouble;
+typedef double vdouble2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) vdouble2 gdouble2;   // (a plain vector: double2's operators are generic-only)
+__device__ __forceinline__ gdouble *held_gs(double *p) {
+    asm volatile("" : "+s"(p));
+    return (gdouble *)p;
+}
 
 // Sum over an aligned group of G lanes; every lane of the group gets the same value.
 template <int G>
@@ -222,6 +243,19 @@ __device__ __forceinline__ void st_row(double *__restrict__ p, const double (&v)
     } else if constexpr (E == 4) {
         reinterpret_cast<double2 *>(p)[0] = make_double2(v[0], v[1]);
         reinterpret_cast<double2 *>(p)[1] = make_double2(v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < E; ++e) p[e] = v[e];
+    }
+}
+
+template <int E>
+__device__ __forceinline__ void st_row(gdouble *__restrict__ p, const double (&v)[E]) {
+    if constexpr (E == 2) {
+        *reinterpret_cast<gdouble2 *>(p) = vdouble2{v[0], v[1]};
+    } else if constexpr (E == 4) {
+        reinterpret_cast<gdouble2 *>(p)[0] = vdouble2{v[0], v[1]};
+        reinterpret_cast<gdouble2 *>(p)[1] = vdouble2{v[2], v[3]};
     } else {
 #pragma unroll
         for (int e = 0; e < E; ++e) p[e] = v[e];
@@ -1337,24 +1371,34 @@ __device__ __forceinline__ void write_partials(double (&acc)[NV], double *__rest
 
 // write_partials for a block of nw <= 8 waves (the latency kernels' run-time block size): the
 // same wave-order sums
-template <int NV>
-__device__ __forceinline__ void write_partials_nw(double (&acc)[NV], double *__restrict__ part, int slot, int nw) {
+// (dst: where thread v < NV stores sum v, write_partials_dst -- the latency kernels' plain
+// instantiations form it before their block barrier)
+template <int NV, typename P>
+__device__ __forceinline__ P write_partials_dst(P part, int slot, int tid = threadIdx.x) {
+    return part + (long)min(tid, NV - 1) * kMaxPartialBlocks + slot;
+}
+template <int NV, typename P>
+__device__ __forceinline__ void write_partials_nw_to(double (&acc)[NV], P dst, int nw, int tid = threadIdx.x) {
     __shared__ double sh[NV][8];
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wid = tid >> 6, lane = tid & 63;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
         const double t = wave_sum(acc[v]);
         if (lane == 0) sh[v][wid] = t;
     }
     __syncthreads();
-    if (threadIdx.x < NV) {
-        const int v = threadIdx.x;
+    if (tid < NV) {
+        const int v = tid;
         double t = 0.0;
 #pragma unroll
         for (int w = 0; w < 8; ++w)
             if (w < nw) t += sh[v][w];
-        part[v * kMaxPartialBlocks + slot] = t;
+        *dst = t;
     }
+}
+template <int NV>
+__device__ __forceinline__ void write_partials_nw(double (&acc)[NV], double *__restrict__ part, int slot, int nw) {
+    write_partials_nw_to<NV>(acc, write_partials_dst<NV>(part, slot), nw);
 }
 
 template <int NV, int NT = kBlock>
@@ -2680,7 +2724,8 @@ __device__ __forceinline__ void wave_reduce_partials(const double *__restrict__ 
 // A in the latency regime (k_it_a MODE 0).  NO: off-diagonal lower entries whose operand
 // rows are prefetched before the barrier (the diagonal entry, the last lower one in the
 // column-sorted adjacency, uses the row's own operands); further ones are loaded after it.
-template <int G, int E, int NO>
+// PLAIN: as in k_lat_b below.
+template <int G, int E, int NO, bool PLAIN = false>
 __global__ void __launch_bounds__(kLatNT) k_lat_a(
     int n, int ld, long foff, const int *__restrict__ adj_ptr, const int *__restrict__ adj_low,
     const int *__restrict__ adj_col, const int *__restrict__ adj_slot, const double *__restrict__ Cw,
@@ -2707,7 +2752,7 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
     // blocks [0, nrb): one row per lane group.  Blocks past nrb: slices of the dense rows --
     // every lane group of the block takes kSliceA consecutive lower entries of one dense row
     // (the rows' own groups skip those entries; A's results are per slot, nothing to combine)
-    const bool slice = (int)blockIdx.x >= nrb;
+    const bool slice = !PLAIN && (int)blockIdx.x >= nrb;
     int i = lat_row_block((int)blockIdx.x, nrb) * rpb + (int)threadIdx.x / G, sq = 0;
     if (slice) {
         const int per = rpb * kSliceA;
@@ -2817,7 +2862,7 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
         // slice of a dense row (no diagonal special case there)
         int eb = kb, nl = valid ? ke - kb : 0;
         if (slice) { eb = kb + sq; nl = valid ? max(0, min(kSliceA, ke - eb)) : 0; }
-        else if (nl > kDenseRow) nl = 0;
+        else if (!PLAIN && nl > kDenseRow) nl = 0;
         const int kd = nl > 0 ? eb + nl - 1 : 0;
         const int jd = adj_col[kd];
         sd = adj_slot[kd];
@@ -2865,13 +2910,38 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
             g_phase_tmp[0][2] = wall_clock64();
 #endif
     }
+    // PLAIN: what the phase after the barrier stores to and branches on
+    gdouble *pD = nullptr, *pRD = nullptr, *pDD = nullptr, *pRec = nullptr, *pPart = nullptr, *pCt = nullptr;
+    int wct = 0, nwh = nwv, fmg = 0, fgl = 0;
+    if constexpr (PLAIN) {
+        pD = held_gs((double *)D);
+        pRD = held_gs((double *)uRD);
+        pDD = held_gs((double *)uDD);
+        pRec = held_gs((double *)rec);
+        pPart = held_gs((double *)partA + (pblk_off + (int)blockIdx.x));
+        pCt = held_gs((double *)ctrl_cur);
+        wct = held_s(pblk_off | (int)blockIdx.x);   // 0: the block that publishes the control block
+        nwh = held_s(nwv);
+        fmg = held_s(__builtin_amdgcn_readfirstlane((fold && mg > 0) ? 1 : 0));
+        fgl = held_s(__builtin_amdgcn_readfirstlane((fold && do_glob && mg > 0) ? 1 : 0));
+    }
     __syncthreads();
     LRS_TS(0, 3);
-    if (pblk_off == 0 && blockIdx.x == 0 && threadIdx.x < C_NCTRL) ctrl_cur[threadIdx.x] = c[threadIdx.x];
+    // (PLAIN: the control block published behind the row stores, or at once when the launch ends here)
+    if constexpr (!PLAIN) {
+        if (pblk_off == 0 && blockIdx.x == 0 && threadIdx.x < C_NCTRL) ctrl_cur[threadIdx.x] = c[threadIdx.x];
+    }
     const bool active = c[C_ACTIVE] != 0.0;
-    if (!active && !(fold && mg > 0)) return;
+    if constexpr (PLAIN) {
+        if (!active && !fmg) {
+            if (wct == 0 && threadIdx.x < C_NCTRL) pCt[threadIdx.x] = c[threadIdx.x];
+            return;
+        }
+    } else {
+        if (!active && !(fold && mg > 0)) return;
+    }
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (fold && do_glob) {
+    if (PLAIN ? fgl != 0 : (fold && do_glob)) {
         // global constraints: A(RR^T) from the slots and their residual (as k_it_a)
         if (gwide) {
             const int lane64 = threadIdx.x & 63;
@@ -2907,7 +2977,102 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
             }
         }
     }
-    if (active && valid) {
+    if constexpr (PLAIN) {
+        if (active && valid) {
+            const int lane = held((int)threadIdx.x) & (G - 1);   // (formed again: one register less across the barrier)
+            DirCoef kc;
+            kc.cg = c[C_CG]; kc.cs0 = c[C_CS0]; kc.cy0 = c[C_CY0]; kc.cs1 = c[C_CS1]; kc.cy1 = c[C_CY1];
+            kc.u0 = (kc.cs0 != 0.0 || kc.cy0 != 0.0);
+            kc.u1 = (kc.cs1 != 0.0 || kc.cy1 != 0.0);
+            const double rho = pl[P_RHO], rhoInv = 1.0 / rho;
+            double yi[E];
+            own.eval(kc, yi);
+            // `entry` below without the lists and without its stores: the slot's sym(R D^T) and
+            // D D^T values to d0 / d1 (the constraint record is formed again from them where it
+            // is stored: the same products)
+            auto pentry = [&](int j, const double (&xjv)[E], const double (&yj)[E], double cwv, double2 l1v, double bv,
+                              double cv, double lv, double &d0o, double &d1o) {
+                double d0 = 0.0, d1 = 0.0;
+                if (j != i) {
+#pragma unroll
+                    for (int e = 0; e < E; ++e) d0 += xi[e] * yj[e] + xjv[e] * yi[e];
+                    d0 *= 0.5;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < E; ++e) d0 += xi[e] * yi[e];
+                }
+#pragma unroll
+                for (int e = 0; e < E; ++e) d1 += yi[e] * yj[e];
+                d0 = group_sum<G>(d0);
+                d1 = group_sum<G>(d1);
+                d0o = d0;
+                d1o = d1;
+                if (lane != 0) return;
+                acc[0] += cwv * d0;
+                acc[1] += cwv * d1;
+                const int c1 = (int)l1v.y;
+                if (c1 < 0) return;
+                const double w = l1v.x;
+                const double q1 = 2.0 * (w * d0), q2 = w * d1;
+                const double q0 = (bv - cv) + rhoInv * lv;
+                acc[2] += q2 * q2; acc[3] += q1 * q2; acc[4] += q0 * q2; acc[5] += q1 * q1;
+                acc[6] += q0 * q1;
+            };
+            auto pstore = [&](int sl, double2 l1v, double bv, double cv, double lv, double d0, double d1) {
+                pRD[sl] = d0;
+                pDD[sl] = d1;
+                const int c1 = (int)l1v.y;
+                if (c1 >= 0) {
+                    const double w = l1v.x;
+                    const double q1 = 2.0 * (w * d0), q2 = w * d1;
+                    gdouble2 *r = reinterpret_cast<gdouble2 *>(pRec + 4L * c1);
+                    r[0] = vdouble2{cv, q1};
+                    r[1] = vdouble2{q2, (-lv) + (-rho) * bv};
+                }
+            };
+            double d0v[NO + 1], d1v[NO + 1];
+#pragma unroll
+            for (int u = 0; u <= NO; ++u) d0v[u] = d1v[u] = 0.0;
+            // adjacency order: the off-diagonal lower entries, then the diagonal (the last)
+#pragma unroll
+            for (int u = 0; u < NO; ++u) {
+                if (u < no) {
+                    double yj[E];
+                    nbr[u].eval(kc, yj);
+                    pentry(jj[u], xj[u], yj, cw[u], l1[u], bq[u], cq[u], lq[u], d0v[u], d1v[u]);
+                }
+            }
+            // a row longer than the window: its further entries are loaded here, and stored as they
+            // come (the row header too, again: a register less through the row phase)
+            for (int k0 = no > NO ? adj_ptr[held(ic)] : 0, k = k0 + NO; k < k0 + no; ++k) {
+                const int j = adj_col[k], sl = adj_slot[k];
+                const long oj = (long)j * ld + lane * E;
+                double xjv[E], yj[E];
+                ld_row<E>(R + oj, xjv);
+                DirRow<E> dj;
+                dj.load(kc, Gc, s0, y0, s1, y1, oj);
+                dj.eval(kc, yj);
+                const double2 l1v = loc1[sl];
+                const int ci = (int)l1v.y;
+                double bv = 0.0, cv = 0.0, lv = 0.0;
+                if (ci >= 0) { bv = b[ci]; cv = cvs[ci]; lv = lam[ci]; }
+                double d0t = 0.0, d1t = 0.0;
+                pentry(j, xjv, yj, Cw[sl], l1v, bv, cv, lv, d0t, d1t);
+                if (lane == 0) pstore(sl, l1v, bv, cv, lv, d0t, d1t);
+            }
+            if (dg) pentry(i, xi, yi, cwd, l1d, bd, cd, lmd, d0v[NO], d1v[NO]);
+            // the stores, in one run
+            st_row<E>(pD + oi, yi);
+            if (lane == 0) {
+#pragma unroll
+                for (int u = 0; u < NO; ++u) {
+                    if (u < no) pstore(ss[u], l1[u], bq[u], cq[u], lq[u], d0v[u], d1v[u]);
+                }
+                if (dg) pstore(sd, l1d, bd, cd, lmd, d0v[NO], d1v[NO]);
+            }
+        }
+        if (wct == 0 && threadIdx.x < C_NCTRL) pCt[threadIdx.x] = c[threadIdx.x];
+    } else if (active && valid) {
         DirCoef kc;
         kc.cg = c[C_CG]; kc.cs0 = c[C_CS0]; kc.cy0 = c[C_CY0]; kc.cs1 = c[C_CS1]; kc.cy1 = c[C_CY1];
         kc.u0 = (kc.cs0 != 0.0 || kc.cy0 != 0.0);
@@ -2979,7 +3144,11 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
         if (dg) entry(i, sd, xi, yi, cwd, l1d, bd, cd, lmd);
     }
     LRS_TS(0, 5);
-    write_partials_nw<8>(acc, partA, pblk_off + blockIdx.x, nwv);
+    if constexpr (PLAIN) {
+        const int tid = held((int)threadIdx.x);   // (formed again here: the prologue's lane ids need not stay live)
+        write_partials_nw_to<8>(acc, write_partials_dst<8>(pPart, 0, tid), nwh, tid);
+    }
+    else write_partials_nw<8>(acc, partA, pblk_off + blockIdx.x, nwv);
     LRS_TS_END(0, 6);
 #ifdef LRS_PHASE_TIMING
     if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -2992,7 +3161,14 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
 // partials and solves the line search while the row waves prefetch the row header, the
 // first NO off-diagonal entries (records and neighbour rows R_j, D_j) and the diagonal
 // entry's records; after the barrier only the tau-dependent arithmetic and the stores run.
-template <int G, int E, int NO>
+// PLAIN (chosen per launch, lat_plain): every slot of the cone has at most one constraint entry
+// and at most one local constraint, no dense-row slice blocks, no dense objective.  The slot
+// lists do not exist there, the parameters come from the block's LDS copy and every store
+// address is formed before the barrier (held in vector registers); after the barrier the row
+// waves consume the prefetched values, do the arithmetic in registers -- `entry`'s, in its order
+// -- and then issue their stores in one run: no scalar load, no load and no wait for a store's
+// acknowledgement behind the first store of a row within the prefetch window.
+template <int G, int E, int NO, bool PLAIN = false>
 __global__ void __launch_bounds__(kLatNT) k_lat_b(
     int n, int ld, long foff, const int *__restrict__ adj_ptr, const int *__restrict__ adj_low,
     const int *__restrict__ adj_col, const int *__restrict__ adj_slot, double *Rb0, double *Rb1,
@@ -3021,7 +3197,7 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
     // blocks [0, nrb): one row per lane group.  Blocks past nrb: slices of the dense rows --
     // every lane group takes kSliceB consecutive entries of one dense row, the block's partial
     // gradient goes to gl[slice] and k_lat_f finishes the row (its own group skips the entries)
-    const bool slice = (int)blockIdx.x >= nrb;
+    const bool slice = !PLAIN && (int)blockIdx.x >= nrb;
     int i = lat_row_block((int)blockIdx.x, nrb) * rpb + (int)threadIdx.x / G, sq = 0;
     if (slice) {
         const int per = rpb * kSliceB;
@@ -3113,7 +3289,7 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
         // updates R), or its slice of a dense row (no diagonal special case there)
         int eb = kb, nt = valid ? ke - kb : 0;
         if (slice) { eb = kb + sq; nt = valid ? max(0, min(kSliceB, ke - eb)) : 0; }
-        else if (nt > kDenseRow) { nt = 0; dense = true; }
+        else if (!PLAIN && nt > kDenseRow) { nt = 0; dense = true; }
         // the diagonal is the last lower entry (columns ascending); positions of the first
         // NO + 1 entries, the off-diagonal ones picked after the diagonal test
         const int kd = (!slice && nt > 0 && kl > kb) ? kl - 1 : 0;
@@ -3172,16 +3348,160 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
             g_phase_tmp[2][6] = wall_clock64();
 #endif
     }
+    // PLAIN: what the phase after the barrier stores to
+    gdouble *pRn = nullptr, *pGn = nullptr, *pSh = nullptr, *pYh = nullptr, *pU = nullptr, *pCv = nullptr;
+    gdouble *pPart = nullptr, *pLs = nullptr;
+    int wls = 0, nwh = nwv;
+    if constexpr (PLAIN) {
+        pRn = held_gs((double *)Rn);
+        pGn = held_gs((double *)Gnew);
+        pSh = held_gs((double *)sh);
+        pYh = held_gs((double *)yh);
+        pU = held_gs((double *)uRR);
+        pCv = held_gs((double *)cvs);
+        pPart = held_gs((double *)partC + (pblk_off + (int)blockIdx.x));
+        pLs = held_gs((double *)ls_cur);
+        wls = held_s(pblk_off | (int)blockIdx.x);   // 0: the block that publishes the line search
+        nwh = held_s(nwv);
+    }
     __syncthreads();
     LRS_TS(2, 2);
-    if (pblk_off == 0 && blockIdx.x == 0 && threadIdx.x < LS_N) ls_cur[threadIdx.x] = ls[threadIdx.x];
-    if (ls[LS_FLAG] != 0.0) return;
-    const double tau = ls[LS_TAU], tau2 = tau * tau, rho = par[P_RHO];
+    // (PLAIN: the line search published behind the row stores, or at once when the launch ends here)
+    if constexpr (!PLAIN) {
+        if (pblk_off == 0 && blockIdx.x == 0 && threadIdx.x < LS_N) ls_cur[threadIdx.x] = ls[threadIdx.x];
+    }
+    if (ls[LS_FLAG] != 0.0) {
+        if constexpr (PLAIN) {
+            if (wls == 0 && threadIdx.x < LS_N) pLs[threadIdx.x] = ls[threadIdx.x];
+        }
+        return;
+    }
+    const double tau = ls[LS_TAU], tau2 = tau * tau;
+    double rho;
+    if constexpr (PLAIN) rho = pl[P_RHO];
+    else rho = par[P_RHO];
     double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     double g[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) g[e] = 0.0;
-    if (valid) {
+    if constexpr (PLAIN) {
+        if (valid) {
+            const int lane = held((int)threadIdx.x) & (G - 1);   // (formed again: one register less across the barrier)
+#pragma unroll
+            for (int e = 0; e < E; ++e) ri[e] += tau * di[e];
+            // `entry` below without the lists and without its stores: the slot's A(R_new R_new^T)
+            // value to dv (the local constraint's value l1u.x * dv is formed again where it is stored)
+            auto pentry = [&](bool lower, const double (&rj)[E], double svv, double2 s1u, double2 ra_, double2 rb_,
+                              double2 l1u, double bv, double &dv) {
+                if ((int)s1u.y >= 0) {
+                    double cv = ra_.x + tau * ra_.y;
+                    cv = cv + tau2 * rb_.x;
+                    const double M1 = rb_.y + rho * cv;
+                    svv += M1 * s1u.x;
+                }
+#pragma unroll
+                for (int e = 0; e < E; ++e) g[e] += svv * rj[e];
+                if (!lower) return;
+                double d = 0.0;
+#pragma unroll
+                for (int e = 0; e < E; ++e) d += ri[e] * rj[e];
+                d = group_sum<G>(d);
+                dv = d;
+                const int cl = (int)l1u.y;
+                if (lane != 0 || cl < 0) return;
+                const double tot = l1u.x * d;
+                const double dd = bv - tot;
+                acc[9] += dd * dd;
+            };
+            auto pstore = [&](int sl, double2 l1u, double d) {
+                pU[sl] = d;
+                const int cl = (int)l1u.y;
+                if (cl >= 0) pCv[cl] = l1u.x * d;
+            };
+            double dv[NO + 1];
+#pragma unroll
+            for (int u = 0; u <= NO; ++u) dv[u] = 0.0;
+            // the off-diagonal entries in adjacency order (prefetched, then the rest), the diagonal last
+#pragma unroll
+            for (int u = 0; u < NO; ++u) {
+                if (u < no) {
+                    double rj[E];
+#pragma unroll
+                    for (int e = 0; e < E; ++e) rj[e] = rjp[u][e] + tau * djp[u][e];
+                    pentry(lw[u], rj, sv[u], s1v[u], ra[u], rb[u], l1v[u], bq[u], dv[u]);
+                }
+            }
+            if (no > NO) {
+                // a row longer than the window: its further entries are loaded here, and stored as they
+                // come (the row header too, again: three registers less through the row phase)
+                const int ih = held(ic);
+                const int kb = adj_ptr[ih], kl = adj_low[ih], ke = adj_ptr[ih + 1];
+                int cnt = 0;
+                for (int k = kb; k < ke; ++k) {
+                    if (dg && k == kl - 1) continue;
+                    if (cnt++ < NO) continue;
+                    const int j = adj_col[k], sl = adj_slot[k];
+                    const long oj = (long)j * ld + lane * E;
+                    double rj[E], dj[E];
+                    ld_row<E>(R + oj, rj);
+                    ld_row<E>(D + oj, dj);
+#pragma unroll
+                    for (int e = 0; e < E; ++e) rj[e] += tau * dj[e];
+                    const double2 s1u = slot1[sl];
+                    const int c1 = (int)s1u.y;
+                    double2 x = make_double2(0.0, 0.0), y = x;
+                    if (c1 >= 0) {
+                        const double2 *r = reinterpret_cast<const double2 *>(rec + 4L * c1);
+                        x = r[0];
+                        y = r[1];
+                    }
+                    const bool lower = k < kl;
+                    const double2 l1u = lower ? loc1[sl] : make_double2(0.0, -1.0);
+                    const int cl = (int)l1u.y;
+                    double dt = 0.0;
+                    pentry(lower, rj, Craw[sl], s1u, x, y, l1u, cl >= 0 ? b[cl] : 0.0, dt);
+                    if (lower && lane == 0) pstore(sl, l1u, dt);
+                }
+            }
+            if (dg) pentry(true, ri, svd, s1d, rad, rbd, l1d, bqd, dv[NO]);
+            // gradient G_new = 2 S R_new, L-BFGS pair s = tau D, y = G_new - G_old, dots
+            double sv2[E], yv[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) g[e] *= 2.0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) { sv2[e] = tau * di[e]; yv[e] = g[e] - go[e]; }
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                acc[0] += g[e] * g[e];
+                acc[1] += yv[e] * sv2[e];
+                acc[2] += yv[e] * yv[e];
+                acc[3] += sv2[e] * g[e];
+                acc[4] += yv[e] * g[e];
+            }
+            if (two) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    acc[5] += sov[e] * g[e];
+                    acc[6] += yov[e] * g[e];
+                    acc[7] += sov[e] * yv[e];
+                    acc[8] += yov[e] * yv[e];
+                }
+            }
+            // the stores, in one run
+            st_row<E>(pRn + oi, ri);
+            st_row<E>(pGn + oi, g);
+            st_row<E>(pSh + oi, sv2);
+            st_row<E>(pYh + oi, yv);
+            if (lane == 0) {
+#pragma unroll
+                for (int u = 0; u < NO; ++u) {
+                    if (u < no && lw[u]) pstore(ss[u], l1v[u], dv[u]);
+                }
+                if (dg) pstore(sd, l1d, dv[NO]);
+            }
+        }
+        if (wls == 0 && threadIdx.x < LS_N) pLs[threadIdx.x] = ls[threadIdx.x];
+    } else if (valid) {
 #pragma unroll
         for (int e = 0; e < E; ++e) ri[e] += tau * di[e];
         if (!slice) st_row<E>(Rn + oi, ri);
@@ -3317,7 +3637,11 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
         }
     }
     LRS_TS(2, 3);
-    write_partials_nw<10>(acc, partC, pblk_off + blockIdx.x, nwv);
+    if constexpr (PLAIN) {
+        const int tid = held((int)threadIdx.x);   // (formed again here: the prologue's lane ids need not stay live)
+        write_partials_nw_to<10>(acc, write_partials_dst<10>(pPart, 0, tid), nwh, tid);
+    }
+    else write_partials_nw<10>(acc, partC, pblk_off + blockIdx.x, nwv);
     LRS_TS_END(2, 4);
 #ifdef LRS_PHASE_TIMING
     if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -6096,12 +6420,16 @@ constexpr int kLatNoA = 2, kLatNoB = 4;   // off-diagonal entries prefetched (A:
 template <int GG, int EE>
 static int res_la() {
     static int c = 0;
-    return resident_blocks(k_lat_a<GG, EE, kLatNoA>, &c, kLatNT);
+    static int cp = 0;   // (either instantiation may be the one launched)
+    return std::min(resident_blocks(k_lat_a<GG, EE, kLatNoA>, &c, kLatNT),
+                    resident_blocks(k_lat_a<GG, EE, kLatNoA, true>, &cp, kLatNT));
 }
 template <int GG, int EE>
 static int res_lb() {
     static int c = 0;
-    return resident_blocks(k_lat_b<GG, EE, kLatNoB>, &c, kLatNT);
+    static int cp = 0;
+    return std::min(resident_blocks(k_lat_b<GG, EE, kLatNoB>, &c, kLatNT),
+                    resident_blocks(k_lat_b<GG, EE, kLatNoB, true>, &cp, kLatNT));
 }
 static bool lat_disabled() {
     static int v = -1;
@@ -6145,6 +6473,14 @@ static LatPlan lat_plan(const DevCone &c, const StagePlan &pa, const StagePlan &
     lp.nf = (int)c.drb_h.size();
     lp.nt = 64 * (w + 1);
     return lp;
+}
+// The PLAIN instantiations of k_lat_a / k_lat_b for this launch: a cone without slot lists
+// (DevCone::plain), without dense-row slice blocks and without the dense objective.
+// LRS_LAT_PLAIN=0 (read per enqueue: diagnostics, tests/test_gpu_lat_plain.py): the general one.
+static bool lat_plain(const DevProblem &P, const DevCone &c, const LatPlan &lp) {
+    const char *e = getenv("LRS_LAT_PLAIN");
+    if (e && e[0] == '0') return false;
+    return c.plain && lp.sa == 0 && lp.sb == 0 && lp.nf == 0 && c.dra_h.empty() && c.drb_h.empty() && !P.ndense;
 }
 // LRS_LAT_ROWWAVES = 1..7 forces the row waves per latency block (0: chosen per launch)
 static int lat_forced_waves() {
@@ -6353,6 +6689,9 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
         lat = false;
     P.last_path = lat ? 0 : 1;
     P.last_tiles = 0;
+    P.last_plain = lat ? 1 : 0;
+    for (int k = 0; k < KL && lat; ++k)
+        if (!lat_plain(P, cone_of(k), lg[k])) P.last_plain = 0;
     for (int k = 0; k < KL; ++k)
         if (tbt[k] || (pa[k].wide && !merge && !tla[k] && cone_of(k).sa_items > 0)) P.last_tiles = 1;
     if (lat) {
@@ -6418,15 +6757,20 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
                        W.uvt2, W.par, ctrl_prev, ctrl_cur, ls_prev, inC, nC, W.part, off, pa[k].T, gwide, c.row0, \
                        pstr)
         if (lat) {
+#define LRS_LAT_A(PL_)                                                                                         \
+    hipLaunchKernelGGL((k_lat_a<GG, EE, kLatNoA, PL_>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown, c.ld, c.foff,   \
+                       c.adj_ptr, c.adj_low, c.adj_col, c.adj_slot, P.Cw, W.R, W.R2, W.D, W.G[0], W.G[1], W.ls[0], \
+                       W.ly[0], W.ls[1], W.ly[1], W.uvt0, W.uvt1, P.loc_ptr, P.loc_con, P.loc_w,                 \
+                       reinterpret_cast<const double2 *>(P.loc1), P.b, W.cvs, W.lam, W.rec, k == 0 ? 1 : 0, P.mg,   \
+                       P.glob, P.m, P.K, P.con_ptr, P.con_slot, P.con_w, W.uvt2, W.par, ctrl_prev, ctrl_cur,       \
+                       ls_prev, inC, nC, W.part, off, gwide, lg[k].nrb, lg[k].nt / 64 - 1, (int)c.dra_h.size(),    \
+                       c.dra)
+            const bool plain = lat_plain(P, c, lg[k]);
             LRS_LAYOUT_SWITCH(c.G, c.E, {
-                hipLaunchKernelGGL((k_lat_a<GG, EE, kLatNoA>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown,
-                                   c.ld, c.foff, c.adj_ptr, c.adj_low, c.adj_col, c.adj_slot, P.Cw, W.R, W.R2, W.D,
-                                   W.G[0], W.G[1], W.ls[0], W.ly[0], W.ls[1], W.ly[1], W.uvt0, W.uvt1, P.loc_ptr,
-                                   P.loc_con, P.loc_w, reinterpret_cast<const double2 *>(P.loc1), P.b, W.cvs, W.lam,
-                                   W.rec, k == 0 ? 1 : 0, P.mg, P.glob, P.m, P.K, P.con_ptr, P.con_slot, P.con_w,
-                                   W.uvt2, W.par, ctrl_prev, ctrl_cur, ls_prev, inC, nC, W.part, off, gwide,
-                                   lg[k].nrb, lg[k].nt / 64 - 1, (int)c.dra_h.size(), c.dra);
+                if (plain) LRS_LAT_A(true);
+                else LRS_LAT_A(false);
             });
+#undef LRS_LAT_A
         } else {
             LRS_LAYOUT_SWITCH(c.G, c.E, {
                 if (split) LRS_LAUNCH_A(1, 1);
@@ -6519,16 +6863,21 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
                        (MM) != 2 && k == 0 ? a.hmirror : nullptr, a.seq, P.ndense ? W.CR : nullptr, W.CD)
         const bool small = pb[k].small;
         if (lat) {
+#define LRS_LAT_B(PL_)                                                                                         \
+    hipLaunchKernelGGL((k_lat_b<GG, EE, kLatNoB, PL_>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown, c.ld, c.foff,   \
+                       c.adj_ptr, c.adj_low, c.adj_col, c.adj_slot, W.R, W.R2, W.D, W.G[0], W.G[1], W.ls[0],       \
+                       W.ly[0], W.ls[1], W.ly[1], W.uvt2, P.Craw, P.slot_ptr, P.slot_con, P.slot_a,               \
+                       reinterpret_cast<const double2 *>(P.slot1), W.rec, P.loc_ptr, P.loc_con, P.loc_w,           \
+                       reinterpret_cast<const double2 *>(P.loc1), P.b, W.cvs, W.par, ctrl_cur, inA, nA, W.partB,    \
+                       P.mg > 0 ? gg : 0, ls_cur, L, W.partC, off, P.m, k == 0 ? a.hmirror : nullptr, a.seq,        \
+                       lg[k].nrb, lg[k].nt / 64 - 1, (int)c.drb_h.size(), c.drb, W.gl + glo,                       \
+                       P.ndense ? W.CR : nullptr, W.CD)
+            const bool plain = lat_plain(P, c, lg[k]);
             LRS_LAYOUT_SWITCH(c.G, c.E, {
-                hipLaunchKernelGGL((k_lat_b<GG, EE, kLatNoB>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown,
-                                   c.ld, c.foff, c.adj_ptr, c.adj_low, c.adj_col, c.adj_slot, W.R, W.R2, W.D, W.G[0],
-                                   W.G[1], W.ls[0], W.ly[0], W.ls[1], W.ly[1], W.uvt2, P.Craw, P.slot_ptr, P.slot_con,
-                                   P.slot_a, reinterpret_cast<const double2 *>(P.slot1), W.rec, P.loc_ptr, P.loc_con,
-                                   P.loc_w, reinterpret_cast<const double2 *>(P.loc1), P.b, W.cvs, W.par, ctrl_cur,
-                                   inA, nA, W.partB, P.mg > 0 ? gg : 0, ls_cur, L, W.partC, off, P.m,
-                                   k == 0 ? a.hmirror : nullptr, a.seq, lg[k].nrb, lg[k].nt / 64 - 1, (int)c.drb_h.size(), c.drb,
-                                   W.gl + glo, P.ndense ? W.CR : nullptr, W.CD);
+                if (plain) LRS_LAT_B(true);
+                else LRS_LAT_B(false);
             });
+#undef LRS_LAT_B
             glo += (long)lg[k].sb * c.ld;
         } else {
             LRS_LAYOUT_SWITCH(c.G, c.E, {

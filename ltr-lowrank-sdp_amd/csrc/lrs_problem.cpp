@@ -1266,6 +1266,15 @@ bool upload_problem(const HostProblem &hp, DevProblem &dp, std::string &err) {
             l1[2L * t + 1] = nl == 0 ? -1.0 : (nl == 1 ? (double)loc_con[loc_ptr[t]] : -2.0);
         }
         if (!dput(&dp.slot1, s1, err) || !dput(&dp.loc1, l1, err)) return false;
+        // a cone none of whose slots needs the lists (the latency kernels' plain instantiations)
+        dp.merged.plain = true;
+        for (int k = 0; k < hp.K; ++k) {
+            DevCone &d = dp.cones[k];
+            d.plain = true;
+            for (int t = d.slot_off; t < d.slot_off + d.P; ++t)
+                if (s1[2L * t + 1] == -2.0 || l1[2L * t + 1] == -2.0) d.plain = false;
+            if (!d.plain) dp.merged.plain = false;
+        }
     }
     dp.mg = (int)glob.size();
     dp.glob_maxlen = 0;

@@ -2897,6 +2897,13 @@ int lrs_get_kernel_path(lrs_ctx *c, int *used) {
     return 0;
 }
 
+int lrs_lat_plain_used(lrs_ctx *c, int *used) {
+    LRS_NEED_CTX(c);
+    LRS_NEED_ARG(used);
+    *used = (c->loaded && c->dp.last_path == 0) ? c->dp.last_plain : 0;
+    return 0;
+}
+
 int lrs_set_log_path(lrs_ctx *c, const char *path) {
     LRS_NEED_CTX(c);
     LRS_NEED_ARG(path);

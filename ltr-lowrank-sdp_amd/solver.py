@@ -122,6 +122,7 @@ def load_library(path=None):
         "lrs_set_kernel_path": (C.c_int, [vp, C.c_int]),
         "lrs_op_dual_infeasibility": (C.c_int, [vp, dp, dp]),
         "lrs_get_kernel_path": (C.c_int, [vp, ip]),
+        "lrs_lat_plain_used": (C.c_int, [vp, ip]),
         "lrs_stage_bytes": (C.c_int, [vp, dp]),
         "lrs_tile_info": (C.c_int, [vp, ip, ip]),
         "lrs_tile_used": (C.c_int, [vp, ip]),
@@ -580,6 +581,12 @@ class Solver:
         v = C.c_int(-1)
         self._check(self.lib.lrs_get_kernel_path(self.ctx, C.byref(v)), "get_kernel_path")
         return v.value
+
+    def lat_plain_used(self):
+        """True when the last enqueued ALM iteration ran the latency kernels' PLAIN instantiation."""
+        v = C.c_int(0)
+        self._check(self.lib.lrs_lat_plain_used(self.ctx, C.byref(v)), "lat_plain_used")
+        return bool(v.value)
 
     def time_stages(self, reps=200):
         """Per-launch ms of the split-iteration stages [A, G, B] (back-to-back relaunches)."""
