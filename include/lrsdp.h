@@ -187,6 +187,40 @@ int lrs_op_dual_infeasibility(lrs_ctx *ctx, double *l1, double *lam_min);
 /* main.c:380-610 flow: ALM phase, ADMM phase, reoptLevel 1/2 rounds (all on the device), dual
  * infeasibility (skipped after a time-limit exit, as main.c:505-510 jumps to END_SOLVING). */
 int lrs_solve(lrs_ctx *ctx, const lrs_params *p, lrs_result *res);
+/* ---- Batched solves: many small instances at once.  No reference counterpart
+ * (the reference's dataset loop runs one process per instance, dataset/run_lorads.sh:85-114).
+ * Every instance whose ALM inner loop is the single-workgroup launch (one
+ * workgroup) stops launching on its own: the members currently in that phase meet, and one
+ * launch per kernel instantiation runs all of them, one block each -- each block computes bit for
+ * bit what the instance's own launch computes.  Every other instance (LP blocks, dense or rank-one
+ * coefficients, lbfgsListLength != 2, multi-launch kernel paths, one workgroup per cone) and every
+ * other phase (ADMM, the dual infeasibility) runs unchanged on the context's own stream.
+ * lrs_solve_batch: n contexts (distinct, same device, unsharded, each with a problem loaded;
+ * n <= LRS_BATCH_MAX), params[n] or one shared set (nparams = 1 or n), res[n], rc[n]: each
+ * instance's own return code and, on failure, its message through lrs_batch_error(b, i).  Returns
+ * 0 when every instance returned 0, else -1 (lrs_last_error() names the first); one failing
+ * instance does not stop the others, and the batch object stays usable.  A refused call (a
+ * duplicate, sharded, unloaded or null context, another device, n out of range) starts nothing.
+ * Each instance runs on a host thread of the call's own.  params' verbose is off inside a batch
+ * (one stdout); lrs_set_log_path still receives each instance's log.  lrs_result's times are wall
+ * clock inside the batch: they include the time an instance spent parked waiting for the others
+ * of its round.  Afterwards every context is as after lrs_solve (lrs_trajectory, lrs_write_json,
+ * lrs_factor_get, ...).
+ * lrs_batch_stats, of the last lrs_solve_batch (each may be NULL): combined launches; the widest
+ * round (blocks launched together, over the round's concurrent launches); members' inner-loop
+ * calls served by combined launches; single-workgroup inner-loop calls that launched alone (the
+ * one-workgroup-per-cone members').
+ * lrs_batch_round_widths: out[w] (w < cap) = rounds of the last call that ran w blocks; *rounds
+ * their number (each may be NULL). */
+#define LRS_BATCH_MAX 256
+typedef struct lrs_batch lrs_batch;
+int lrs_batch_create(lrs_batch **out);
+void lrs_batch_destroy(lrs_batch *b);
+int lrs_solve_batch(lrs_batch *b, lrs_ctx **ctxs, int n, const lrs_params *params, int nparams,
+                    lrs_result *res, int *rc);
+const char *lrs_batch_error(lrs_batch *b, int i);
+int lrs_batch_stats(lrs_batch *b, long *launches, int *widest, long *served, long *alone);
+int lrs_batch_round_widths(lrs_batch *b, long *out, int cap, long *rounds);
 /* trajectory (phase 1 then phase 2) after lrs_solve: curr and oracle ranks */
 int lrs_trajectory(lrs_ctx *ctx, int phase, int *curr_rank, int *oracle_rank, int cap);
 /* JSON like lorads_logging.c:618-712 */

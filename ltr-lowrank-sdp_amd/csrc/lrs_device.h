@@ -435,6 +435,22 @@ bool small_alm_fits(const DevProblem &P, DevWork &W);
 int small_alm_workgroups(const DevProblem &P, DevWork &W);
 int launch_small_alm(const DevProblem &P, DevWork &W, const double *ctrl_in, double *ctrl_out, double *ls_out,
                      hipStream_t st);
+// The same loop for many contexts at once (lrs_solve_batch): member i's launch
+// arguments as launch_small_alm would form them, the launches combined by kernel instantiation,
+// one block a member.  host_ctrl receives the member's final control block (C_NCTRL doubles).
+// launch_small_alm_batch returns when the round's launches and copies have completed; the
+// members' streams must be idle.  *launches is advanced by the combined launches made, *widest
+// raised to the largest one's blocks.
+struct SmallBatch;
+struct SmallBatchMember {
+    const DevProblem *P;
+    DevWork *W;
+    const double *ctrl_in;
+    double *ctrl_out, *ls_out, *host_ctrl;
+};
+int small_batch_create(SmallBatch **out, int cap);
+void small_batch_destroy(SmallBatch *b);
+int launch_small_alm_batch(SmallBatch *b, const SmallBatchMember *mem, int n, int *launches);
 
 // ---- device-resident CG (lrs_kernels.hip "Device-resident CG") ----
 enum CgIdx { CG_ACTIVE = 0, CG_ITERS, CG_BNORM, CG_RR, CG_QTR0, CG_QTR1, CG_TOTAL, CG_N = 8 };

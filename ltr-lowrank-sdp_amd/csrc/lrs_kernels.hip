@@ -7089,8 +7089,11 @@ __device__ __forceinline__ bool xwg_sum(const SmallArgs &A, int wg, unsigned &xe
 #define LRS_SM_MARK(v) do { } while (0)
 #define LRS_SM_SUB(q, v) do { } while (0)
 #endif
-template <int LD, bool AL, bool MC>
-__global__ void __launch_bounds__(kSmallThreads) k_small_alm(SmallArgs A) {
+// The loop itself, shared by the solo launch (k_small_alm: A is the kernel argument) and the
+// batched one (k_small_alm_batch: A is this block's entry of the launch's table, a reference
+// into the constant address space -- ARGS is the reference type).
+template <int LD, bool AL, bool MC, class ARGS>
+__device__ __forceinline__ void small_alm_body(ARGS A) {
     constexpr int LS = LD + 2;          // LDS row stride (doubles): 16-B aligned rows
     constexpr int H = LD / 2;           // double2 per row
     constexpr int LS2 = LS / 2;
@@ -7403,7 +7406,7 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_alm(SmallArgs A) {
                 for (int q = 0; q < 7; ++q) (mc ? xsum : red)[q] = s7[q];
             }
         }
-        if (mc) {
+        if constexpr (MC) {
             __syncthreads();
             if (wv == 0 && !xwg_sum(A, wg, xe, 7, xsum, xrecv, red) && lane == 0) xfail = 1;
         }
@@ -7634,7 +7637,7 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_alm(SmallArgs A) {
             if (tid == 0)
                 for (int q = 0; q < 10; ++q) (mc ? xsum : red)[q] = s10[q];
         }
-        if (mc) {
+        if constexpr (MC) {
             __syncthreads();
             if (wv == 0 && !xwg_sum(A, wg, xe, 10, xsum, xrecv, red) && lane == 0) xfail = 1;
         }
@@ -7675,6 +7678,27 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_alm(SmallArgs A) {
     if (tid == 0 && wg == 0)
         for (int q = 0; q < 16; ++q) g_phase[3][q] += sm_t[q];
 #endif
+}
+template <int LD, bool AL, bool MC>
+__global__ void __launch_bounds__(kSmallThreads) k_small_alm(SmallArgs A) {
+    small_alm_body<LD, AL, MC, const SmallArgs &>(A);
+}
+// B independent instances in one launch (lrs_solve_batch): block b runs tab[b]
+// through the loop above, one workgroup each (nwg == 1 members only: no block waits on another),
+// so each computes bitwise what its solo launch computes.  The table is written before the
+// launch and by no kernel: it is read through the constant address space, like the solo
+// kernel's argument segment -- uniform scalar loads that the compiler may repeat wherever it
+// needs a field again.  (A private copy of the entry went to scratch, ~1 KB a lane: its arrays
+// are indexed by loop variables.)  The block's
+// final control block also goes to mirror[b] (each thread re-reads the element it wrote), so the
+// host fetches a launch's control blocks in one copy.
+template <int LD, bool AL>
+__global__ void __launch_bounds__(kSmallThreads) k_small_alm_batch(const SmallArgs *__restrict__ tab,
+                                                                   double *__restrict__ mirror) {
+    typedef const __attribute__((address_space(4))) SmallArgs CArgs;
+    CArgs &A = *(CArgs *)(unsigned long long)(tab + blockIdx.x);
+    small_alm_body<LD, AL, false, CArgs &>(A);
+    if (threadIdx.x < C_NCTRL) mirror[(long)blockIdx.x * 64 + threadIdx.x] = A.ctrl_out[threadIdx.x];
 }
 
 static size_t small_lds_bytes(int N, int ld, int Ptot, long nadj, bool al) {
@@ -7778,6 +7802,12 @@ static int launch_small_ld(const SmallArgs &A, size_t lds, hipStream_t st) {
     LRS_CHECK_LAUNCH();
     return 0;
 }
+static void small_alm_env(SmallArgs &A) {
+    const char *e = getenv("LRS_XWG_SPIN");
+    A.spin_log2 = e ? std::max(-1, std::min(40, atoi(e))) : 26;   // -1: no wait at all (tests)
+    const char *o = getenv("LRS_SMALL_ROWSORT");
+    A.row_sort = o ? (atoi(o) != 0) : 1;
+}
 // One launch: the inner loop from the control block at ctrl_in to its exit; the final control
 // block to ctrl_out, the last line search to ls_out, the iterate to W.R.
 int launch_small_alm(const DevProblem &P, DevWork &W, const double *ctrl_in, double *ctrl_out, double *ls_out,
@@ -7791,12 +7821,7 @@ int launch_small_alm(const DevProblem &P, DevWork &W, const double *ctrl_in, dou
     A.ctrl_in = ctrl_in;
     A.ctrl_out = ctrl_out;
     A.ls_out = ls_out;
-    {
-        const char *e = getenv("LRS_XWG_SPIN");
-        A.spin_log2 = e ? std::max(-1, std::min(40, atoi(e))) : 26;   // -1: no wait at all (tests)
-        const char *o = getenv("LRS_SMALL_ROWSORT");
-        A.row_sort = o ? (atoi(o) != 0) : 1;
-    }
+    small_alm_env(A);
     size_t lds = small_lds_bytes(A.N, ld, A.Ptot, A.nadj, A.al != 0);
     if (A.nwg > 1) {   // the largest cone's
         lds = 0;
@@ -7818,6 +7843,143 @@ int launch_small_alm(const DevProblem &P, DevWork &W, const double *ctrl_in, dou
     if (A.al) { LRS_SMALL_LD(true, false) }
     LRS_SMALL_LD(false, false)
 #undef LRS_SMALL_LD
+}
+
+// ---- batched launch (lrs_solve_batch): one round of the rendezvous ----
+constexpr int kSmallBatchStreams = 4;
+struct SmallBatch {
+    int cap = 0;
+    hipStream_t st[kSmallBatchStreams] = {};
+    SmallArgs *htab = nullptr, *dtab = nullptr;   // the round's table: pinned, device
+    double *hctl = nullptr, *dctl = nullptr;      // the members' final control blocks ([cap][64])
+    std::vector<int> order, ld;
+    std::vector<size_t> lds;
+};
+void small_batch_destroy(SmallBatch *b) {
+    if (!b) return;
+    for (hipStream_t s : b->st)
+        if (s) (void)hipStreamDestroy(s);
+    if (b->htab) (void)hipHostFree(b->htab);
+    if (b->hctl) (void)hipHostFree(b->hctl);
+    if (b->dtab) (void)hipFree(b->dtab);
+    if (b->dctl) (void)hipFree(b->dctl);
+    delete b;
+}
+int small_batch_create(SmallBatch **out, int cap) {
+    SmallBatch *b = new SmallBatch();
+    b->cap = cap;
+    bool ok = true;
+    for (hipStream_t &s : b->st) ok = ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && hipHostMalloc((void **)&b->htab, sizeof(SmallArgs) * cap, 0) == hipSuccess;
+    ok = ok && hipHostMalloc((void **)&b->hctl, sizeof(double) * 64 * cap, 0) == hipSuccess;
+    ok = ok && hipMalloc((void **)&b->dtab, sizeof(SmallArgs) * cap) == hipSuccess;
+    ok = ok && hipMalloc((void **)&b->dctl, sizeof(double) * 64 * cap) == hipSuccess;
+    if (!ok) {
+        snprintf(g_err, sizeof(g_err), "batched inner loop: stream or table allocation failed");
+        small_batch_destroy(b);
+        return -1;
+    }
+    *out = b;
+    return 0;
+}
+template <int LD, bool AL>
+static int launch_small_batch_ld(const SmallArgs *tab, double *mirror, int nblk, size_t lds, hipStream_t st) {
+    static bool attr = false;
+    if (!attr) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_small_alm_batch<LD, AL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallMaxDynLds) != hipSuccess) {
+            snprintf(g_err, sizeof(g_err), "batched inner loop: LDS attribute refused");
+            return -1;
+        }
+        attr = true;
+    }
+    hipLaunchKernelGGL((k_small_alm_batch<LD, AL>), dim3(nblk), dim3(kSmallThreads), lds, st, tab, mirror);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+// One round: the n members' inner loops (each as launch_small_alm would run it alone on one
+// workgroup), grouped by (factor row width, adjacency in LDS), one launch per group with the
+// group's largest dynamic LDS, the groups on up to four streams.  The caller has made every
+// member's earlier work complete (its stream synchronised).  Returns after the launches and the
+// copies of the final control blocks (to host_ctrl of each member) have completed, so the table
+// and the mirrors are free for the next round.
+int launch_small_alm_batch(SmallBatch *b, const SmallBatchMember *mem, int n, int *launches) {
+    if (n <= 0 || n > b->cap) {
+        snprintf(g_err, sizeof(g_err), "batched inner loop: %d members (capacity %d)", n, b->cap);
+        return -1;
+    }
+    b->order.resize(n); b->ld.resize(n); b->lds.resize(n);
+    std::vector<SmallArgs> args(n);
+    for (int i = 0; i < n; ++i) {
+        SmallArgs &A = args[i];
+        A = SmallArgs{};
+        if (!small_alm_args(*mem[i].P, *mem[i].W, A, &b->ld[i]) || A.nwg != 1) {
+            snprintf(g_err, sizeof(g_err), "batched inner loop: member %d does not fit one workgroup", i);
+            return -1;
+        }
+        A.ctrl_in = mem[i].ctrl_in;
+        A.ctrl_out = mem[i].ctrl_out;
+        A.ls_out = mem[i].ls_out;
+        small_alm_env(A);
+        b->lds[i] = small_lds_bytes(A.N, b->ld[i], A.Ptot, A.nadj, A.al != 0);
+        b->order[i] = i;
+    }
+    auto key = [&](int i) { return b->ld[i] * 2 + (args[i].al ? 1 : 0); };
+    std::stable_sort(b->order.begin(), b->order.end(), [&](int x, int y) { return key(x) < key(y); });
+    for (int q = 0; q < n; ++q) b->htab[q] = args[b->order[q]];
+    int ngroups = 0;
+    unsigned used = 0;
+    // an error part-way: nothing may still read the table when the caller reuses it
+    auto bail = [&](int rc) {
+        for (int si = 0; si < kSmallBatchStreams; ++si)
+            if ((used >> si) & 1u) (void)hipStreamSynchronize(b->st[si]);
+        return rc;
+    };
+    for (int q0 = 0; q0 < n;) {
+        int q1 = q0;
+        size_t lds = 0;
+        while (q1 < n && key(b->order[q1]) == key(b->order[q0])) lds = std::max(lds, b->lds[b->order[q1++]]);
+        const int nb = q1 - q0, si = ngroups % kSmallBatchStreams;
+        hipStream_t st = b->st[si];
+        used |= 1u << si;
+        if (hipMemcpyAsync(b->dtab + q0, b->htab + q0, sizeof(SmallArgs) * nb, hipMemcpyHostToDevice, st) != hipSuccess) {
+            snprintf(g_err, sizeof(g_err), "batched inner loop: table upload failed");
+            return bail(-1);
+        }
+        const SmallArgs *tab = b->dtab + q0;
+        double *mir = b->dctl + 64L * q0;
+        const bool al = args[b->order[q0]].al != 0;
+        int rc;
+#define LRS_BATCH_LD(AL)                                                            \
+    switch (b->ld[b->order[q0]]) {                                                  \
+    case 8: rc = launch_small_batch_ld<8, AL>(tab, mir, nb, lds, st); break;        \
+    case 16: rc = launch_small_batch_ld<16, AL>(tab, mir, nb, lds, st); break;      \
+    case 24: rc = launch_small_batch_ld<24, AL>(tab, mir, nb, lds, st); break;      \
+    case 32: rc = launch_small_batch_ld<32, AL>(tab, mir, nb, lds, st); break;      \
+    case 48: rc = launch_small_batch_ld<48, AL>(tab, mir, nb, lds, st); break;      \
+    default: rc = launch_small_batch_ld<64, AL>(tab, mir, nb, lds, st); break;      \
+    }
+        if (al) { LRS_BATCH_LD(true) } else { LRS_BATCH_LD(false) }
+#undef LRS_BATCH_LD
+        if (rc) return bail(rc);
+        if (hipMemcpyAsync(b->hctl + 64L * q0, mir, sizeof(double) * 64 * nb, hipMemcpyDeviceToHost, st) != hipSuccess) {
+            snprintf(g_err, sizeof(g_err), "batched inner loop: control copy failed");
+            return bail(-1);
+        }
+        ngroups++;
+        q0 = q1;
+    }
+    for (int si = 0; si < kSmallBatchStreams; ++si)
+        if ((used >> si) & 1u) {
+            const hipError_t e = hipStreamSynchronize(b->st[si]);
+            if (e != hipSuccess) {
+                snprintf(g_err, sizeof(g_err), "batched inner loop: %s", hipGetErrorString(e));
+                return -1;
+            }
+        }
+    for (int q = 0; q < n; ++q) memcpy(mem[b->order[q]].host_ctrl, b->hctl + 64L * q, sizeof(double) * C_NCTRL);
+    if (launches) *launches += ngroups;
+    return 0;
 }
 
 // Sharded solve: pack the listed rows (ld doubles each) into a contiguous buffer.

@@ -28,6 +28,7 @@
 #include <rccl/rccl.h>
 
 #include "../../include/lrsdp.h"
+#include "lrs_batch_rdv.h"
 #include "lrs_device.h"
 #include "lrs_problem.h"
 
@@ -224,6 +225,24 @@ struct lrs_ctx {
     std::vector<double> ring_beta;
     long ring_len = 0;
     double dinf_time = 0.0;
+    // member of a running lrs_solve_batch (else null): the group and this context's index in it
+    struct lrs_batch *batch = nullptr;
+    int batch_idx = -1;
+};
+
+// A batched solve (lrs_solve_batch): the members' rendezvous, the combined
+// launcher's streams and tables, each member's submission of the current round, its error text.
+struct lrs_batch {
+    BatchRendezvous rdv;
+    SmallBatch *sb = nullptr;
+    int device = -1;
+    std::vector<SmallBatchMember> sub;
+    std::vector<std::string> errs;
+    std::string round_err;        // written by the round's leader before it wakes the members
+    int launches = 0;             // combined launches (the leader of a round, one round at a time)
+    std::atomic<long> alone{0};   // single-workgroup inner-loop calls that launched on their own
+    std::vector<long> hist;       // rounds by width, of the last call
+    bool busy = false;
 };
 
 // ------------------------------------------------------------------------
@@ -1756,7 +1775,29 @@ static int run_inner(lrs_ctx *c, const lrs_params *p, double rho, double rctol, 
     // the single-workgroup inner loop (small problems): the whole call is one launch
     bool small = !c->prof && use_small(c);
     bool fell_back = false;
-    if (small) {
+    // a member of a batched solve is in the rendezvous' quorum exactly while its inner-loop calls
+    // are one-workgroup launches (a rank change can move a member either way)
+    const bool batched = c->batch && small && small_alm_workgroups(c->dp, c->W) == 1;
+    if (c->batch) {
+        if (batched) c->batch->rdv.enter(c->batch_idx);
+        else c->batch->rdv.leave(c->batch_idx);
+    }
+    if (batched) {
+        // no launch of its own: the call's arguments go to the round that the last member to park
+        // launches for all (one block each).  The stream's earlier work (the control block just
+        // put, the dual update, the gradient) completes first: the round's streams take no event.
+        lrs_batch *b = c->batch;
+        HIPC(hipStreamSynchronize(c->st));
+        b->sub[c->batch_idx] = SmallBatchMember{&c->dp, &c->W, c->W.ctrl + C_NCTRL, c->W.ctrl + C_NCTRL, c->W.lsres,
+                                                c->hpin + kHpCtrl};
+        if (b->rdv.submit(c->batch_idx)) { set_err("batched inner loop: %s", b->round_err.c_str()); return -1; }
+        res = c->hpin + kHpCtrl;
+        if ((int)res[C_EXIT] == EXIT_XWG) { set_err("single-workgroup inner loop: exchange timed out"); return -1; }
+        enq = std::max(0L, (long)res[C_INNER] - io.inner);
+        c->dp.last_path = 4;
+        if (c->stats) c->st_batches++;
+    } else if (small) {
+        if (c->batch) c->batch->alone++;
         // one workgroup per cone: the workgroups hand sums to each other through device memory,
         // which assumes they are co-resident; another stream or context holding the CUs can delay
         // one past the exchange's spin limit (EXIT_XWG).  The state the loop writes is kept
@@ -2104,7 +2145,21 @@ static void alm_log(lrs_ctx *c, const lrs_params *p, const AlmState &st, double 
 
 // LORADS_ALMOptimize, lorads_alm.c:1220-1484
 static int alm_optimize_body(lrs_ctx *c, const lrs_params *p, AlmState &st, double tss);
+// The ALM phase of a member of a batched solve: in the rendezvous' quorum from here (where its
+// inner loop is the one-workgroup launch) to every exit of the phase, error returns included.
+struct BatchQuorum {
+    lrs_ctx *c;
+    explicit BatchQuorum(lrs_ctx *c_) : c(c_) {
+        if (!c->batch) return;
+        if (!c->prof && use_small(c) && small_alm_workgroups(c->dp, c->W) == 1) c->batch->rdv.enter(c->batch_idx);
+        else c->batch->rdv.leave(c->batch_idx);
+    }
+    ~BatchQuorum() { if (c->batch) c->batch->rdv.leave(c->batch_idx); }
+    BatchQuorum(const BatchQuorum &) = delete;
+    BatchQuorum &operator=(const BatchQuorum &) = delete;
+};
 static int alm_optimize(lrs_ctx *c, const lrs_params *p, AlmState &st, double tss) {
+    BatchQuorum quorum(c);
     c->st_calls = c->st_batches = c->st_iters = c->st_nop = 0;
     c->st_inner_s = 0;
     const double t0 = now_s();
@@ -2786,7 +2841,10 @@ static int reopt(lrs_ctx *c, lrs_params *p, AlmState &alm, AdmmState &admm, doub
     p->maxADMMIter = admm_iter;
     if (obj_scale(c, reopt_param)) return -1;
     if (admm.rho <= p->rhoMax) alm.rho = std::max(admm.rho, alm.rho);
-    if (alm_optimize_reopt(c, p, alm, std::sqrt(p->ALMRhoFactor), tss) < 0) return -1;
+    {
+        BatchQuorum quorum(c);
+        if (alm_optimize_reopt(c, p, alm, std::sqrt(p->ALMRhoFactor), tss) < 0) return -1;
+    }
     p->rhoMax = std::max(std::sqrt(std::max(admm.rho, alm.rho) / admm.rho) * admm.rho, p->rhoMax);
     if (alm_to_admm(c, p, alm, admm)) return -1;
     if (*bad == 0 || level < 2) {
@@ -3566,6 +3624,126 @@ int lrs_solve(lrs_ctx *c, const lrs_params *p, lrs_result *res) {
     LRS_NEED_ARG(p);
     LRS_NEED_ARG(res);
     return solve_impl(c, p, res);
+}
+
+// ---- batched solves
+int lrs_batch_create(lrs_batch **out) {
+    LRS_NEED_ARG(out);
+    *out = new lrs_batch();
+    return 0;
+}
+void lrs_batch_destroy(lrs_batch *b) {
+    if (!b) return;
+    if (b->sb) {
+        (void)hipSetDevice(b->device);
+        small_batch_destroy(b->sb);
+    }
+    delete b;
+}
+int lrs_solve_batch(lrs_batch *b, lrs_ctx **ctxs, int n, const lrs_params *params, int nparams, lrs_result *res,
+                    int *rc) {
+    LRS_NEED_ARG(b);
+    LRS_NEED_ARG(ctxs);
+    LRS_NEED_ARG(params);
+    LRS_NEED_ARG(res);
+    LRS_NEED_ARG(rc);
+    // every refusal comes before the first thread starts
+    if (n < 1 || n > LRS_BATCH_MAX) { set_err("lrs_solve_batch: %d instances (1 to %d)", n, LRS_BATCH_MAX); return -1; }
+    if (nparams != 1 && nparams != n) { set_err("lrs_solve_batch: %d parameter sets for %d instances (1 or %d)", nparams, n, n); return -1; }
+    if (b->busy) { set_err("lrs_solve_batch: the batch object is in use"); return -1; }
+    for (int i = 0; i < n; ++i) {
+        lrs_ctx *c = ctxs[i];
+        if (!c) { set_err("lrs_solve_batch: instance %d: null context", i); return -1; }
+        if (!c->loaded) { set_err("lrs_solve_batch: instance %d: no problem loaded", i); return -1; }
+        if (sharded(c)) { set_err("lrs_solve_batch: instance %d: a sharded context cannot join a batch", i); return -1; }
+        if (c->device != ctxs[0]->device) {
+            set_err("lrs_solve_batch: instance %d is on device %d, instance 0 on device %d", i, c->device, ctxs[0]->device);
+            return -1;
+        }
+        if (c->batch) { set_err("lrs_solve_batch: instance %d is a member of a running batch", i); return -1; }
+        for (int j = 0; j < i; ++j)
+            if (ctxs[j] == c) { set_err("lrs_solve_batch: instances %d and %d are the same context", j, i); return -1; }
+    }
+    bind(ctxs[0]);
+    if (b->sb && b->device != ctxs[0]->device) {
+        (void)hipSetDevice(b->device);
+        small_batch_destroy(b->sb);
+        b->sb = nullptr;
+        bind(ctxs[0]);
+    }
+    if (!b->sb) {
+        OPC(small_batch_create(&b->sb, LRS_BATCH_MAX));
+        b->device = ctxs[0]->device;
+    }
+    b->busy = true;
+    b->sub.assign(n, SmallBatchMember{});
+    b->errs.assign(n, std::string());
+    b->round_err.clear();
+    b->launches = 0;
+    b->alone = 0;
+    b->rdv.reset(n, [b](const std::vector<int> &mem) -> int {
+        std::vector<SmallBatchMember> m;
+        m.reserve(mem.size());
+        for (int i : mem) m.push_back(b->sub[i]);
+        const int r = launch_small_alm_batch(b->sb, m.data(), (int)m.size(), &b->launches);
+        if (r) b->round_err = last_device_error();
+        return r;
+    });
+    // every member counts towards the quorum until its solve decides otherwise (its ALM phase takes
+    // another inner loop, or it fails before that phase), so the first round waits for all of them
+    for (int i = 0; i < n; ++i) b->rdv.enter(i);
+    std::vector<std::thread> th;
+    th.reserve(n);
+    for (int i = 0; i < n; ++i)
+        th.emplace_back([=] {
+            lrs_ctx *c = ctxs[i];
+            bind(c);
+            lrs_params prm = params[nparams == 1 ? 0 : i];
+            prm.verbose = 0;   // one stdout for all members: the per-context log file still gets the lines
+            c->batch = b;
+            c->batch_idx = i;
+            rc[i] = solve_impl(c, &prm, &res[i]);
+            b->rdv.leave(i);
+            c->batch = nullptr;
+            c->batch_idx = -1;
+            if (rc[i]) b->errs[i] = g_lrs_err;
+        });
+    for (auto &t : th) t.join();
+    b->hist = b->rdv.width_histogram();
+    b->busy = false;
+    bind(ctxs[0]);
+    int bad = 0, first = -1;
+    for (int i = 0; i < n; ++i)
+        if (rc[i]) { if (!bad++) first = i; }
+    if (bad) {
+        set_err("lrs_solve_batch: %d of %d instances failed (first: instance %d: %s)", bad, n, first, b->errs[first].c_str());
+        return -1;
+    }
+    return 0;
+}
+const char *lrs_batch_error(lrs_batch *b, int i) {
+    if (!b || i < 0 || i >= (int)b->errs.size()) return "";
+    return b->errs[i].c_str();
+}
+int lrs_batch_stats(lrs_batch *b, long *launches, int *widest, long *served, long *alone) {
+    LRS_NEED_ARG(b);
+    long rounds = 0;
+    b->rdv.stats(&rounds, widest, served);
+    if (launches) *launches = b->launches;
+    if (alone) *alone = b->alone.load();
+    return 0;
+}
+int lrs_batch_round_widths(lrs_batch *b, long *out, int cap, long *rounds) {
+    LRS_NEED_ARG(b);
+    long tot = 0;
+    for (int w = 0; w < (int)b->hist.size(); ++w) {
+        if (out && w < cap) out[w] = b->hist[w];
+        tot += b->hist[w];
+    }
+    if (out)
+        for (int w = (int)b->hist.size(); w < cap; ++w) out[w] = 0;
+    if (rounds) *rounds = tot;
+    return 0;
 }
 
 int lrs_trajectory(lrs_ctx *c, int phase, int *curr, int *orc, int cap) {

@@ -6,8 +6,12 @@
 // flags the reference never implemented (--rankSchedule, --nearStallFactor,
 // --disableOracle) and --device.  The solve runs on the MI355X
 // through liblrsdp.so (include/lrsdp.h).
+// `--batch FILE` solves many instances in this one process (lrs_solve_batch): each non-empty
+// line of FILE is `<instance.dat-s> <jsonfile> [flags...]`, the line's flags parsed by the same
+// table on top of the command line's.  Exit code 1 if any instance failed (named on stderr).
 #include <getopt.h>
 
+#include <cctype>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,12 +55,14 @@ static std::string problem_name(const char *path) {   // set_problem_name, lorad
     return s;
 }
 
-int main(int argc, char **argv) {
+// the flags of one instance: the command line's, then (--batch) its manifest line's on top
+struct Flags {
     lrs_params p;
-    lrs_params_default(&p);
-    p.verbose = 1;
-    const char *logFile = nullptr, *jsonFile = nullptr, *schedFile = nullptr;
+    std::string logFile, jsonFile, schedFile, batchFile;
     int device = 0;
+};
+static void parse_flags(int argc, char **argv, Flags &F) {
+    lrs_params &p = F.p;
     static struct option opts[] = {
         {"logfile", required_argument, 0, 1025}, {"jsonfile", required_argument, 0, 1026},
         {"initRho", required_argument, 0, 1000}, {"rhoMax", required_argument, 0, 1001},
@@ -74,17 +80,13 @@ int main(int argc, char **argv) {
         {"oracleRankNaive", no_argument, 0, 1021},
         {"rankSchedule", required_argument, 0, 2000}, {"nearStallFactor", required_argument, 0, 2001},
         {"disableOracle", no_argument, 0, 2002}, {"device", required_argument, 0, 2003},
-        {"quiet", no_argument, 0, 2004}, {0, 0, 0, 0}};
-    if (argc < 2) {
-        fprintf(stderr, "usage: %s <file.dat-s> [--flag value ...]\n", argv[0]);
-        return 0;
-    }
-    const char *fname = argv[1];
+        {"quiet", no_argument, 0, 2004}, {"batch", required_argument, 0, 2005}, {0, 0, 0, 0}};
     int opt, li = 0;
+    optind = 0;   // a fresh scan (one per manifest line)
     while ((opt = getopt_long(argc, argv, "r:", opts, &li)) != -1) {
         switch (opt) {
-        case 1025: logFile = optarg; break;
-        case 1026: jsonFile = optarg; break;
+        case 1025: F.logFile = optarg; break;
+        case 1026: F.jsonFile = optarg; break;
         case 1000: p.initRho = atof(optarg); break;
         case 1001: p.rhoMax = atof(optarg); break;
         case 1002: p.rhoCellingALM = atof(optarg); break;
@@ -110,27 +112,172 @@ int main(int argc, char **argv) {
         case 1019: p.dyrankLevel = atoi(optarg); break;
         case 1020: p.highAccMode = atoi(optarg); break;
         case 1021: p.oracleRankNaive = 1; break;
-        case 2000: schedFile = optarg; break;
+        case 2000: F.schedFile = optarg; break;
         case 2001: p.nearStallFactor = atof(optarg); break;
         case 2002: p.disableOracle = 1; break;
-        case 2003: device = atoi(optarg); break;
+        case 2003: F.device = atoi(optarg); break;
         case 2004: p.verbose = 0; break;
+        case 2005: F.batchFile = optarg; break;
         default: break;   // unknown flags: getopt already printed a message; ignored like main.c
         }
     }
-    std::vector<int> sched;
-    if (schedFile) {
-        if (parse_schedule(schedFile, sched)) {
+}
+// what follows the scan: the schedule file (sched keeps the array p points to), the L-BFGS floor
+static void finish_flags(Flags &F, std::vector<int> &sched) {
+    lrs_params &p = F.p;
+    if (!F.schedFile.empty()) {
+        if (parse_schedule(F.schedFile.c_str(), sched)) {
             p.rankSchedule = sched.data();
             p.rankScheduleLen = (int)sched.size();
         } else {
-            fprintf(stderr, "[lrsdp] could not parse rank schedule %s; ignored\n", schedFile);
+            fprintf(stderr, "[lrsdp] could not parse rank schedule %s; ignored\n", F.schedFile.c_str());
         }
     }
     if (p.lbfgsListLength < 1) {   // the reference's ring needs one node at least (data/lorads_solver.c:686-706)
         fprintf(stderr, "[lrsdp] lbfgsListLength %d < 1; using 2\n", p.lbfgsListLength);
         p.lbfgsListLength = 2;
     }
+}
+
+// --batch FILE: load every line's instance, one lrs_solve_batch, one JSON each
+static int run_batch(const Flags &base, const char *prog) {
+    FILE *f = fopen(base.batchFile.c_str(), "r");
+    if (!f) {
+        fprintf(stderr, "[lrsdp] cannot open batch file %s\n", base.batchFile.c_str());
+        return 1;
+    }
+    struct Job {
+        Flags F;
+        std::string inst;
+        std::vector<int> sched;
+        lrs_ctx *ctx = nullptr;
+        bool ok = false;
+    };
+    std::vector<Job *> jobs;
+    std::string text;
+    char buf[4096];
+    size_t nr;
+    while ((nr = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, nr);
+    fclose(f);
+    int failed = 0;
+    for (size_t pos = 0; pos < text.size();) {
+        size_t e = text.find('\n', pos);
+        if (e == std::string::npos) e = text.size();
+        std::string line = text.substr(pos, e - pos);
+        pos = e + 1;
+        std::vector<std::string> tok;
+        for (size_t i = 0; i < line.size();) {
+            while (i < line.size() && isspace((unsigned char)line[i])) i++;
+            size_t j = i;
+            while (j < line.size() && !isspace((unsigned char)line[j])) j++;
+            if (j > i) tok.push_back(line.substr(i, j - i));
+            i = j;
+        }
+        if (tok.empty()) continue;
+        if (tok.size() < 2) {
+            fprintf(stderr, "[lrsdp] batch line `%s`: expected <instance.dat-s> <jsonfile> [flags...]\n", line.c_str());
+            failed++;
+            continue;
+        }
+        Job *j = new Job();
+        j->F = base;
+        j->F.batchFile.clear();
+        j->inst = tok[0];
+        std::vector<char *> av;
+        av.push_back(const_cast<char *>(prog));
+        for (size_t q = 2; q < tok.size(); ++q) av.push_back(const_cast<char *>(tok[q].c_str()));
+        av.push_back(nullptr);
+        parse_flags((int)av.size() - 1, av.data(), j->F);
+        j->F.jsonFile = tok[1];
+        finish_flags(j->F, j->sched);
+        jobs.push_back(j);
+    }
+    if ((int)jobs.size() > LRS_BATCH_MAX) {
+        fprintf(stderr, "[lrsdp] batch file %s: %zu instances (at most %d)\n", base.batchFile.c_str(), jobs.size(),
+                LRS_BATCH_MAX);
+        return 1;
+    }
+    std::vector<lrs_ctx *> ctxs;
+    std::vector<lrs_params> prm;
+    std::vector<Job *> live;
+    for (Job *j : jobs) {
+        if (lrs_ctx_create(base.device, &j->ctx) || lrs_load_sdpa(j->ctx, j->inst.c_str(), nullptr)) {
+            fprintf(stderr, "[lrsdp] batch: %s failed: %s\n", j->inst.c_str(), lrs_last_error());
+            failed++;
+            continue;
+        }
+        if (!j->F.logFile.empty() && j->F.logFile != base.logFile) lrs_set_log_path(j->ctx, j->F.logFile.c_str());
+        ctxs.push_back(j->ctx);
+        prm.push_back(j->F.p);
+        live.push_back(j);
+    }
+    if (!live.empty()) {
+        lrs_batch *b = nullptr;
+        std::vector<lrs_result> res(live.size());
+        std::vector<int> rc(live.size(), 0);
+        if (lrs_batch_create(&b)) {
+            fprintf(stderr, "[lrsdp] %s\n", lrs_last_error());
+            return 1;
+        }
+        const int ret = lrs_solve_batch(b, ctxs.data(), (int)live.size(), prm.data(), (int)live.size(), res.data(), rc.data());
+        if (ret && lrs_last_error()[0] && !rc.empty()) {
+            bool any = false;
+            for (int v : rc) any = any || v != 0;
+            if (!any) {   // the call itself was refused
+                fprintf(stderr, "[lrsdp] batch: %s\n", lrs_last_error());
+                failed += (int)live.size();
+                live.clear();
+            }
+        }
+        for (size_t q = 0; q < live.size(); ++q) {
+            Job *j = live[q];
+            if (rc[q]) {
+                fprintf(stderr, "[lrsdp] batch: %s failed: %s\n", j->inst.c_str(), lrs_batch_error(b, (int)q));
+                failed++;
+                continue;
+            }
+            const std::string pid = problem_name(j->inst.c_str());
+            if (lrs_write_json(j->ctx, j->F.jsonFile.c_str(), pid.c_str(), j->inst.c_str(), &res[q], &j->F.p)) {
+                fprintf(stderr, "[lrsdp] batch: %s failed: %s\n", j->inst.c_str(), lrs_last_error());
+                failed++;
+                continue;
+            }
+            printf("%s: pObj %10.6e dObj %10.6e ALM inner %ld ADMM %ld all_time %f -> %s\n", pid.c_str(), res[q].pobj,
+                   res[q].dobj, res[q].alm_inner, res[q].admm_iter, res[q].solve_time, j->F.jsonFile.c_str());
+        }
+        long launches = 0, served = 0, alone = 0;
+        int widest = 0;
+        lrs_batch_stats(b, &launches, &widest, &served, &alone);
+        printf("batch: %zu instances, %ld combined launches (widest round %d), %ld inner-loop calls served, %ld alone\n",
+               live.size(), launches, widest, served, alone);
+        lrs_batch_destroy(b);
+    }
+    for (Job *j : jobs) {
+        if (j->ctx) lrs_ctx_destroy(j->ctx);
+        delete j;
+    }
+    if (failed) fprintf(stderr, "[lrsdp] batch: %d instance(s) failed\n", failed);
+    return failed ? 1 : 0;
+}
+
+int main(int argc, char **argv) {
+    Flags F;
+    lrs_params_default(&F.p);
+    F.p.verbose = 1;
+    if (argc < 2) {
+        fprintf(stderr, "usage: %s <file.dat-s> [--flag value ...]\n       %s --batch FILE [--flag value ...]\n", argv[0],
+                argv[0]);
+        return 0;
+    }
+    const char *fname = argv[1];
+    parse_flags(argc, argv, F);
+    std::vector<int> sched;
+    if (!F.batchFile.empty()) return run_batch(F, argv[0]);
+    finish_flags(F, sched);
+    lrs_params &p = F.p;
+    const char *logFile = F.logFile.empty() ? nullptr : F.logFile.c_str();
+    const char *jsonFile = F.jsonFile.empty() ? nullptr : F.jsonFile.c_str();
+    const int device = F.device;
     printf("-----------------------------------------------------------\n");
     printf("  LoRADS-compatible low-rank SDP solver on MI355X (%s)\n", lrs_version());
     printf("-----------------------------------------------------------\n");

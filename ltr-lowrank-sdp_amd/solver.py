@@ -151,6 +151,12 @@ def load_library(path=None):
         "lrs_shard_comm_record": (C.c_int, [vp, C.c_int]),
         "lrs_xwg_fallbacks": (C.c_int, [vp, ip]),
         "lrs_shard_comm_log": (C.c_int, [vp, C.POINTER(C.c_long), C.c_long, C.POINTER(C.c_long)]),
+        "lrs_batch_create": (C.c_int, [C.POINTER(vp)]),
+        "lrs_batch_destroy": (None, [vp]),
+        "lrs_solve_batch": (C.c_int, [vp, C.POINTER(vp), C.c_int, C.POINTER(Params), C.c_int, C.POINTER(Result), ip]),
+        "lrs_batch_error": (C.c_char_p, [vp, C.c_int]),
+        "lrs_batch_stats": (C.c_int, [vp, C.POINTER(C.c_long), ip, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+        "lrs_batch_round_widths": (C.c_int, [vp, C.POINTER(C.c_long), C.c_int, C.POINTER(C.c_long)]),
         "lrs_shard_plan": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_long), ip, ip, ip, ip, ip, ip, ip]),
     }
     for name, (res, args) in sig.items():
@@ -525,6 +531,15 @@ class Solver:
                 "R": self.get_factor(R), "G": self.get_factor(G), "cvs": self.get_vec(CVS),
                 "lam": self.get_vec(LAMBDA), "s": self.get_factor(pair[0]), "y": self.get_factor(pair[1])}
 
+    def alm_last_step(self):
+        """(tau, ||G||^2, pinf, beta) of the last completed ALM inner trip of the last solve
+        and the newest L-BFGS pair's (s, y) selectors (lrs_alm_last_step)."""
+        out = (C.c_double * 4)()
+        nw = C.c_int()
+        self._check(self.lib.lrs_alm_last_step(self.ctx, out, C.byref(nw)), "alm_last_step")
+        return {"tau": out[0], "lag": out[1], "pinf": out[2], "beta": out[3],
+                "pair": (S0, Y0) if nw.value == 0 else (S1, Y1)}
+
     def get_rank(self):
         out = (C.c_int * self.K)()
         self._check(self.lib.lrs_get_rank(self.ctx, out), "get_rank")
@@ -716,6 +731,149 @@ def shard_plan(path, world, rank):
         raise RuntimeError(lib.lrs_last_error().decode())
     out = {k: v[:n_] for (k, v), n_ in zip(arr.items(), (world + 1, nl, world + 1, ns, nsh, ml, ml))}
     out.update(n=n, row0=r0, nown=nown)
+    return out
+
+
+BATCH_MAX = 256   # LRS_BATCH_MAX of include/lrsdp.h
+
+
+class BatchError(RuntimeError):
+    """lrs_solve_batch returned -1: .rc and .errors per instance, .results of those that solved."""
+
+    def __init__(self, msg, rc, errors, results):
+        super().__init__(msg)
+        self.rc, self.errors, self.results = rc, errors, results
+
+
+class Batch:
+    """A batched solve of many Solvers at once (include/lrsdp.h lrs_solve_batch): the instances on
+    the single-workgroup inner loop share launches, one workgroup each."""
+
+    def __init__(self):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        if self.lib.lrs_batch_create(C.byref(self.h)) != 0:
+            raise RuntimeError(f"batch_create: {self.lib.lrs_last_error().decode()}")
+
+    def close(self):
+        if self.h:
+            self.lib.lrs_batch_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self, solvers, params=None, raise_on_failure=True):
+        """params: None (defaults), one dict for all, or a list of one dict per solver.  Returns
+        the list of result dicts; when an instance failed, raises BatchError (or, with
+        raise_on_failure=False, returns None in its place; see .rc / .errors)."""
+        n = len(solvers)
+        if params is None or isinstance(params, dict):
+            plist = [default_params(**(params or {}))]
+        else:
+            if len(params) != n:
+                raise ValueError("one parameter dict per solver")
+            plist = [default_params(**(q or {})) for q in params]
+        parr = (Params * len(plist))(*plist)
+        ctxs = (C.c_void_p * max(n, 1))(*[sv.ctx for sv in solvers])
+        res = (Result * max(n, 1))()
+        rc = (C.c_int * max(n, 1))()
+        for q in range(max(n, 1)):
+            rc[q] = -2   # not run (a refused call starts nothing)
+        ret = self.lib.lrs_solve_batch(self.h, ctxs, n, parr, len(plist), res, rc)
+        self.rc = list(rc)[:n]
+        self.errors = [self.lib.lrs_batch_error(self.h, q).decode() if self.rc[q] not in (0, -2) else ""
+                       for q in range(n)]
+        out = [res[q].as_dict() if self.rc[q] == 0 else None for q in range(n)]
+        del plist   # (kept alive until here: rank schedules)
+        if ret != 0 and raise_on_failure:
+            raise BatchError(self.lib.lrs_last_error().decode(), self.rc, self.errors, out)
+        return out
+
+    def stats(self):
+        la, se, al = C.c_long(), C.c_long(), C.c_long()
+        wi = C.c_int()
+        if self.lib.lrs_batch_stats(self.h, C.byref(la), C.byref(wi), C.byref(se), C.byref(al)) != 0:
+            raise RuntimeError(self.lib.lrs_last_error().decode())
+        return {"launches": la.value, "widest": wi.value, "served": se.value, "alone": al.value}
+
+    def round_widths(self):
+        """{width: rounds} of the last solve."""
+        h = (C.c_long * (BATCH_MAX + 1))()
+        if self.lib.lrs_batch_round_widths(self.h, h, BATCH_MAX + 1, None) != 0:
+            raise RuntimeError(self.lib.lrs_last_error().decode())
+        return {w: h[w] for w in range(BATCH_MAX + 1) if h[w]}
+
+
+_batch = None
+
+
+def _default_batch():
+    global _batch
+    if _batch is None:
+        _batch = Batch()
+    return _batch
+
+
+def solve_batch(solvers, params=None, **kw):
+    """Solve every Solver of the list at once (Batch.solve on the module's own batch object)."""
+    return _default_batch().solve(solvers, params, **kw)
+
+
+def batch_stats():
+    """Counters of the last solve_batch (launches, widest, served, alone)."""
+    return _default_batch().stats()
+
+
+def run_lorads_batch(jobs, params, near_stall_factor=0.7, timeout=3600, device=0):
+    """run_lorads for many instances in ONE process of the MI355X binary (--batch): jobs is a
+    list of (instance_path, json_output_path) or (instance_path, json_output_path, fixed_rank,
+    rank_schedule_path); params as for run_lorads, shared.  Returns run_lorads' triple per job."""
+    if not BIN_PATH.exists():
+        raise RuntimeError(f"binary not built: {BIN_PATH}")
+    jobs = [tuple(j) + (None,) * (4 - len(j)) for j in jobs]
+    lines = []
+    for inst, js, fixed_rank, sched in jobs:
+        if fixed_rank is not None and sched is not None:
+            raise ValueError("fixed_rank and rank_schedule_path are mutually exclusive")
+        Path(js).parent.mkdir(parents=True, exist_ok=True)
+        Path(js).unlink(missing_ok=True)   # an earlier run's file is no result of this one
+        line =[str(inst), str(js)]
+        if sched is not None:
+            line += ["--rankSchedule", str(sched), "--nearStallFactor", str(near_stall_factor)]
+        elif fixed_rank is not None:
+            line += ["--fixedRank", str(fixed_rank)]
+        if any(any(ch.isspace() for ch in tok) for tok in line):
+            raise ValueError("a batch manifest separates fields by blanks: no blanks in paths")
+        lines.append(" ".join(line))
+    import tempfile
+    with tempfile.NamedTemporaryFile("w", suffix=".batch", delete=False) as f:
+        f.write("\n".join(lines) + "\n")
+        manifest = f.name
+    cmd = [str(BIN_PATH), "--batch", manifest]
+    for k, v in params.items():
+        cmd += [f"--{k}", str(v)]
+    cmd += ["--disableOracle", "--device", str(device)]
+    try:
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+        if r.returncode != 0:
+            print(f"  [error] lorads --batch: {r.stderr[:400]}")
+    except subprocess.TimeoutExpired:
+        print("  [error] lorads --batch timed out")
+    finally:
+        os.unlink(manifest)
+    out = []
+    for inst, js, _fr, _sc in jobs:
+        try:
+            with open(js) as f:
+                m = json.load(f)
+            m = m.get("final_metrics", m.get("metrics", {}))
+            out.append((True, m.get("solve_time_sec"), m.get("primal_obj", m.get("primal_objective"))))
+        except Exception:
+            out.append((False, None, None))
     return out
 
 
