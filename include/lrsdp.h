@@ -259,7 +259,10 @@ int lrs_set_log_path(lrs_ctx *ctx, const char *path);
  * 0 = automatic (the latency-regime kernels k_lat_a/k_lat_b when every row's lane group is
  * resident at once, else the general row kernels), 1 = general row kernels only,
  * 2 = general row kernels in their bandwidth-regime form (stages split in two launches),
- * 3 = as 2 with the long-row neighbour kernels k_wide_a/k_wide_b wherever the layout allows.
+ * 3 = as 2 with the long-row neighbour kernels k_wide_a/k_wide_b wherever the layout allows,
+ * 4 = the single-workgroup inner loop where it fits, 5 = as 0 with one lane group a row even
+ * where denser rows would get a team of lane groups, so that the latency-regime kernels also take
+ * such cones (diagnostics and tests: the teams are the faster form there).
  * The environment variable LRS_NO_LAT=1 forces 1 for every context. */
 int lrs_set_kernel_path(lrs_ctx *ctx, int path);
 /* The path the last enqueued ALM inner iteration of this context took (0 latency-regime
@@ -270,6 +273,10 @@ int lrs_get_kernel_path(lrs_ctx *ctx, int *used);
  * one local constraint, without dense-row slices and without a dense objective), else 0.  The
  * environment variable LRS_LAT_PLAIN=0 selects the general instantiation (same results). */
 int lrs_lat_plain_used(lrs_ctx *ctx, int *used);
+/* *used = 1 when the last enqueued ALM inner iteration ran the latency kernels (path 0) with their
+ * wave sums as transposed butterflies (wave_tsum: the same pair tree as one wave sum a value, so
+ * the same bits), else 0.  The environment variable LRS_LAT_TSUM=0 selects one wave sum a value. */
+int lrs_lat_tsum_used(lrs_ctx *ctx, int *used);
 
 /* Standalone A(UU^T) on R (the constraint-entry kernel k_auv_con, all cones): reps
  * launches back to back between two HIP events, average ms per launch; and its
@@ -292,6 +299,12 @@ int lrs_mfma_f64_peak(lrs_ctx *ctx, double *tflops);
  * rate separated from the clock (bench.py "mfma_probe").  No reference counterpart. */
 int lrs_mfma_f64_probe(lrs_ctx *ctx, int waves_per_simd, int chains, double *tflops, double *mhz,
                        double *cycles_per_mfma);
+/* The latency kernels' two wave-sum forms on the caller's inputs, one small launch: `ref` from one
+ * wave sum a value, `out` from the transposed butterfly (nv values each, 1 <= nv <= 16), for a
+ * bitwise comparison.  form 0, the control wave's prologue: in[nv][n], the partials of
+ * 1 <= n <= 256 producer blocks.  form 1, the block tail: in[nv][64 n], the accumulators of the
+ * threads of 1 <= n <= 8 waves; value v summed per wave, then over the waves in wave order. */
+int lrs_wave_tsum_probe(lrs_ctx *ctx, int form, int nv, int n, const double *in, double *ref, double *out);
 
 /* Dense objective (a cone whose C is kept as a full n x n matrix: LRS_DENSE_C=1, or n >= 1024
  * with C filling >= 1/4 of the lower triangle): ms per C R product on the FP64 matrix cores

@@ -226,11 +226,12 @@ struct ShardHooks {
 
 struct DevProblem {
     const ShardHooks *shard = nullptr;   // non-null in a sharded solve
-    int no_lat = 0;                      // kernel path (lrs_set_kernel_path): 1 never the latency kernels, 2 + bandwidth regime, 3 + long-row kernels, 4 the single-workgroup inner loop
+    int no_lat = 0;                      // kernel path (lrs_set_kernel_path): 1 never the latency kernels, 2 + bandwidth regime, 3 + long-row kernels, 4 the single-workgroup inner loop, 5 auto without teams
     int *slot_g = nullptr;               // [Ptot][2] every slot's (row, col) in the all-cones row space
     mutable int last_path = -1;          // path of the last enqueued iteration (0 lat, 1 general)
     mutable int last_tiles = 0;          // the last enqueued iteration ran stage A / B over the 2-D tiles
     mutable int last_plain = 0;          // ... every latency launch of it as the PLAIN instantiation
+    mutable int last_tsum = 0;           // ... its latency launches' wave sums by wave_tsum (LRS_LAT_TSUM)
     int m = 0, K = 0;
     int lp_cone = -1;   // the LP block's cone (the last), -1 without one
     long NRpad = 0;     // factor buffer length (doubles)
@@ -367,6 +368,7 @@ int launch_gram(const DevProblem &P, int cone, const double *X, const double *Y,
 // sustained v_mfma_f64_16x16x4f64 rate: every CU, 2 waves a SIMD, 8 accumulators a wave
 int mfma_f64_peak(hipStream_t st, double *tflops);
 int mfma_f64_probe(hipStream_t st, int wps, int chains, double *tflops, double *mhz, double *cyc_per_mfma);
+int wave_tsum_probe(hipStream_t st, int form, int nv, int n, const double *in, double *ref, double *out);
 // dense objective of cone `cone` (DevCone::Cd): Y = scale C X + beta Y on the cone's rows
 // (X, Y full factor buffers; columns r..ld of Y written 0)
 int launch_dense_cx(const DevProblem &P, int cone, const double *X, double *Y, double beta, hipStream_t st);

@@ -221,6 +221,99 @@ __device__ __forceinline__ double wave_sum(double v) {
     return (read_lane(v, 0) + read_lane(v, 16)) + (read_lane(v, 32) + read_lane(v, 48));
 }
 
+// ------------------------------------------------------------------------
+// Transposed wave sums: NV <= 16 values a lane, every one summed over the wave's 64 lanes by
+// wave_sum's own pair tree -- lane pairs (xor 1), quads (xor 2), eights (row_half_mirror),
+// sixteens (row_mirror), then (row0 + row1) + (row2 + row3) -- so every total has wave_sum's
+// bits (IEEE addition is commutative: an exchange that pairs the same two subtrees gives the
+// same sum).  Where wave_sum carries all 64 lanes' copies of one value through every step, a
+// step here halves the values a lane holds (a reduce-scatter, as group_sum4): of the slot pair
+// (2j, 2j + 1) a lane keeps the one its step bit h selects and adds the partner's copy of it.
+// The mirror steps pair lane i with 7 - i and 15 - i, so the step bits are combined from the
+// lane bits b0..b3 such that partners of a later step agree on all earlier ones:
+//   h0 = b0 ^ b2, h1 = b1 ^ b2, h2 = b2 ^ b3, h3 = b3.
+// After the four row steps the lane with step bits h holds the row sum of value
+// h0 + 2 h1 + 4 h2 + 8 h3 (fewer than 16 values: the steps left over are plain all-reduce
+// steps and the high bits do not select).  A slot pair past NV is skipped; the odd slot's
+// missing partner is a padding +0.0 that only ever meets the partner lane's padding.
+// NV = 10: 11 double moves and 13 additions where ten wave_sums take 40 moves, 40 readlane
+// pairs and 70 additions.
+constexpr int tsum_slots(int nv) { return nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 8 ? 8 : 16; }
+constexpr int tsum_half(int live) { return live == 1 ? 1 : (live + 1) / 2; }
+__device__ __forceinline__ int tsum_bits(int lane) {
+    const int b2 = (lane >> 2) & 1, b3 = (lane >> 3) & 1;
+    return ((lane & 3) ^ (b2 * 3)) | ((b2 ^ b3) << 2) | (b3 << 3);
+}
+// the value whose total wave_tsum<NV> leaves in this lane / whether this lane is the one of
+// lanes 0..15 that stores it
+template <int NV>
+__device__ __forceinline__ int tsum_index(int lane) {
+    return tsum_bits(lane) & (tsum_slots(NV) - 1);
+}
+template <int NV>
+__device__ __forceinline__ bool tsum_owner(int lane) {
+    return lane < 16 && tsum_bits(lane) < NV;
+}
+template <int CTRL, int LIVE>
+__device__ __forceinline__ void tsum_step(double *a, bool h) {
+    if constexpr (LIVE == 1) {
+        a[0] += dpp_mov<CTRL>(a[0]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < (LIVE + 1) / 2; ++j) {
+            const double lo = a[2 * j], hi = 2 * j + 1 < LIVE ? a[2 * j + 1] : 0.0;
+            a[j] = (h ? hi : lo) + dpp_mov<CTRL>(h ? lo : hi);
+        }
+    }
+}
+// (a + b with a = the even rows' / the lower half's value in every lane: wave_sum's operand order)
+__device__ __forceinline__ double tsum_rows(double v) {
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
+#ifndef LRS_TSUM_SHFL
+    // v_permlane16_swap / v_permlane32_swap of a register with its copy: the first result has the
+    // even rows' (the lower half's) value in both rows of a pair, the second the odd rows'
+    const auto l16 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto h16 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    const double s = __longlong_as_double(((long long)h16[0] << 32) | l16[0]) +
+                     __longlong_as_double(((long long)h16[1] << 32) | l16[1]);
+    const long long c = __double_as_longlong(s);
+    const unsigned lo2 = (unsigned)c, hi2 = (unsigned)(c >> 32);
+    const auto l32 = __builtin_amdgcn_permlane32_swap(lo2, lo2, false, false);
+    const auto h32 = __builtin_amdgcn_permlane32_swap(hi2, hi2, false, false);
+    return __longlong_as_double(((long long)h32[0] << 32) | l32[0]) +
+           __longlong_as_double(((long long)h32[1] << 32) | l32[1]);
+#else
+    (void)lo; (void)hi;
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+#endif
+}
+// Every lane: the wave total of value tsum_index<NV>(lane).
+template <int NV>
+__device__ __forceinline__ double wave_tsum(const double (&x)[NV], int lane) {
+    static_assert(NV >= 1 && NV <= 16, "1..16 values");
+    const int h = tsum_bits(lane);
+    double a[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) a[v] = x[v];
+    constexpr int L1 = tsum_half(NV), L2 = tsum_half(L1), L3 = tsum_half(L2);
+    tsum_step<0xB1, NV>(a, (h & 1) != 0);
+    tsum_step<0x4E, L1>(a, (h & 2) != 0);
+    tsum_step<0x141, L2>(a, (h & 4) != 0);
+    tsum_step<0x140, L3>(a, (h & 8) != 0);
+    return tsum_rows(a[0]);
+}
+// The totals to LDS, lds[v] == wave_sum(x[v]) bit for bit: the lanes that hold them store them in
+// one instruction (readers of the same wave behind a wave barrier: every lane gets every total
+// from a broadcast read, in vector registers -- 2 NV v_readlane would put them in scalar ones).
+template <int NV>
+__device__ __forceinline__ void wave_tsum_to(const double (&x)[NV], int lane, double *lds) {
+    const double t = wave_tsum<NV>(x, lane);
+    if (tsum_owner<NV>(lane)) lds[tsum_index<NV>(lane)] = t;
+}
+
 template <int E>
 __device__ __forceinline__ void ld_row(const double *__restrict__ p, double (&v)[E]) {
     if constexpr (E == 2) {
@@ -1350,14 +1443,21 @@ __device__ void line_search(const double *__restrict__ par, int K, const double 
 // Block sums of NV accumulators into part[v][slot]: wave sums meet in LDS, then thread v
 // adds value v over the waves in wave order (the order of block_reduce) and stores it --
 // one barrier, the NV sums in parallel.
+// ts (block-uniform): the wave sums by wave_tsum, the lane that holds value v stores it (same bits).
 template <int NV, int NT = kBlock>
-__device__ __forceinline__ void write_partials(double (&acc)[NV], double *__restrict__ part, int slot) {
+__device__ __forceinline__ void write_partials(double (&acc)[NV], double *__restrict__ part, int slot,
+                                               bool ts = false) {
     __shared__ double sh[NV][NT / 64];
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (ts) {
+        const double t = wave_tsum<NV>(acc, lane);
+        if (tsum_owner<NV>(lane)) sh[tsum_index<NV>(lane)][wid] = t;
+    } else {
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const double t = wave_sum(acc[v]);
-        if (lane == 0) sh[v][wid] = t;
+        for (int v = 0; v < NV; ++v) {
+            const double t = wave_sum(acc[v]);
+            if (lane == 0) sh[v][wid] = t;
+        }
     }
     __syncthreads();
     if (threadIdx.x < NV) {
@@ -1373,18 +1473,30 @@ __device__ __forceinline__ void write_partials(double (&acc)[NV], double *__rest
 // same wave-order sums
 // (dst: where thread v < NV stores sum v, write_partials_dst -- the latency kernels' plain
 // instantiations form it before their block barrier)
+// ts (block-uniform): the wave sums by wave_tsum.  zero (wave-uniform, with ts): this wave's
+// accumulators are +0.0 by construction, so it stores wave_sum(+0.0) = +0.0 without summing.
 template <int NV, typename P>
 __device__ __forceinline__ P write_partials_dst(P part, int slot, int tid = threadIdx.x) {
     return part + (long)min(tid, NV - 1) * kMaxPartialBlocks + slot;
 }
 template <int NV, typename P>
-__device__ __forceinline__ void write_partials_nw_to(double (&acc)[NV], P dst, int nw, int tid = threadIdx.x) {
+__device__ __forceinline__ void write_partials_nw_to(double (&acc)[NV], P dst, int nw, int tid = threadIdx.x,
+                                                     bool ts = false, bool zero = false) {
     __shared__ double sh[NV][8];
     const int wid = tid >> 6, lane = tid & 63;
+    if (ts) {
+        if (zero) {
+            if (lane < NV) sh[lane][wid] = 0.0;
+        } else {
+            const double t = wave_tsum<NV>(acc, lane);
+            if (tsum_owner<NV>(lane)) sh[tsum_index<NV>(lane)][wid] = t;
+        }
+    } else {
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const double t = wave_sum(acc[v]);
-        if (lane == 0) sh[v][wid] = t;
+        for (int v = 0; v < NV; ++v) {
+            const double t = wave_sum(acc[v]);
+            if (lane == 0) sh[v][wid] = t;
+        }
     }
     __syncthreads();
     if (tid < NV) {
@@ -1397,8 +1509,9 @@ __device__ __forceinline__ void write_partials_nw_to(double (&acc)[NV], P dst, i
     }
 }
 template <int NV>
-__device__ __forceinline__ void write_partials_nw(double (&acc)[NV], double *__restrict__ part, int slot, int nw) {
-    write_partials_nw_to<NV>(acc, write_partials_dst<NV>(part, slot), nw);
+__device__ __forceinline__ void write_partials_nw(double (&acc)[NV], double *__restrict__ part, int slot, int nw,
+                                                  bool ts = false) {
+    write_partials_nw_to<NV>(acc, write_partials_dst<NV>(part, slot), nw, threadIdx.x, ts);
 }
 
 template <int NV, int NT = kBlock>
@@ -2682,6 +2795,7 @@ __device__ __forceinline__ int lat_row_block(int b, int nrb) {
 // 9.55 us, scripts/gpu_r04v.sh).
 constexpr int kLatNT = 512;                      // the largest block (launch bounds)
 constexpr int kLatRowWaves = kLatNT / 64 - 1;
+constexpr int kLatZeroBit = 16;                  // beside a block's wave count (<= 8): a wave that sums zeros
 constexpr int kLatRows = kLatRowWaves * 64;      // row-wave threads of the largest block
 constexpr int kLatMaxPartials = 256;             // producer blocks one control wave reduces
 constexpr int kSliceA = 2;                       // lower entries per lane group in a dense-row slice of A
@@ -2713,6 +2827,28 @@ __device__ __forceinline__ void sum_partials(const double (&x)[kLatQ][NV], int n
         out[v] = wave_sum(a);
     }
 }
+// the per-lane sums over q that sum_partials hands to wave_sum (the same masking)
+template <int NV>
+__device__ __forceinline__ void presum_partials(const double (&x)[kLatQ][NV], int nblk, double *a) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        double t = 0.0;
+#pragma unroll
+        for (int q = 0; q < kLatQ; ++q) t += (lane + 64 * q < nblk) ? x[q][v] : 0.0;
+        a[v] = t;
+    }
+}
+// sum_partials with the wave sums by wave_tsum, through lds[NV]: the same bits
+template <int NV>
+__device__ __forceinline__ void tsum_partials(const double (&x)[kLatQ][NV], int nblk, double *lds, double (&out)[NV]) {
+    double a[NV];
+    presum_partials<NV>(x, nblk, a);
+    wave_tsum_to<NV>(a, threadIdx.x & 63, lds);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int v = 0; v < NV; ++v) out[v] = lds[v];
+}
 template <int NV>
 __device__ __forceinline__ void wave_reduce_partials(const double *__restrict__ part, int nblk, double (&out)[NV]) {
     double x[kLatQ][NV];
@@ -2725,7 +2861,7 @@ __device__ __forceinline__ void wave_reduce_partials(const double *__restrict__ 
 // rows are prefetched before the barrier (the diagonal entry, the last lower one in the
 // column-sorted adjacency, uses the row's own operands); further ones are loaded after it.
 // PLAIN: as in k_lat_b below.
-template <int G, int E, int NO, bool PLAIN = false>
+template <int G, int E, int NO, bool PLAIN = false, bool TS = false>
 __global__ void __launch_bounds__(kLatNT) k_lat_a(
     int n, int ld, long foff, const int *__restrict__ adj_ptr, const int *__restrict__ adj_low,
     const int *__restrict__ adj_col, const int *__restrict__ adj_slot, const double *__restrict__ Cw,
@@ -2742,6 +2878,7 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
     double *__restrict__ partA, int pblk_off, int gwide, int nrb, int lrw, int nda, const int *__restrict__ dra) {
     __shared__ double c[C_NCTRL];
     __shared__ double pl[P_NPAR];
+    __shared__ double sred[10];   // TS: the control wave's totals
     LRS_TS(0, 0);
     LRS_BLK_BEGIN();
     // lrw row waves + the control wave (an argument beside nrb, loaded in the first argument batch:
@@ -2823,7 +2960,8 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
         if (l64 < P_NPAR) pl[l64] = pvv;
         double s[10];
         if (fold) {
-            sum_partials<10>(px, nblkC, s);
+            if constexpr (TS) tsum_partials<10>(px, nblkC, sred, s);
+            else sum_partials<10>(px, nblkC, s);
         } else {
 #pragma unroll
             for (int v = 0; v < 10; ++v) s[v] = 0.0;
@@ -2921,9 +3059,12 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
         pPart = held_gs((double *)partA + (pblk_off + (int)blockIdx.x));
         pCt = held_gs((double *)ctrl_cur);
         wct = held_s(pblk_off | (int)blockIdx.x);   // 0: the block that publishes the control block
-        nwh = held_s(nwv);
         fmg = held_s(__builtin_amdgcn_readfirstlane((fold && mg > 0) ? 1 : 0));
         fgl = held_s(__builtin_amdgcn_readfirstlane((fold && do_glob && mg > 0) ? 1 : 0));
+        // TS, kLatZeroBit beside the wave count (one scalar register for both): this wave's
+        // accumulators stay +0.0 -- the control wave has no row and, without the global
+        // constraints' loop below, adds nothing
+        nwh = held_s(nwv | (TS && ctrl_wave && !fgl ? kLatZeroBit : 0));
     }
     __syncthreads();
     LRS_TS(0, 3);
@@ -3146,9 +3287,10 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
     LRS_TS(0, 5);
     if constexpr (PLAIN) {
         const int tid = held((int)threadIdx.x);   // (formed again here: the prologue's lane ids need not stay live)
-        write_partials_nw_to<8>(acc, write_partials_dst<8>(pPart, 0, tid), nwh, tid);
+        write_partials_nw_to<8>(acc, write_partials_dst<8>(pPart, 0, tid), TS ? nwh & (kLatZeroBit - 1) : nwh, tid, TS,
+                                TS && (nwh & kLatZeroBit) != 0);
     }
-    else write_partials_nw<8>(acc, partA, pblk_off + blockIdx.x, nwv);
+    else write_partials_nw<8>(acc, partA, pblk_off + blockIdx.x, nwv, TS);
     LRS_TS_END(0, 6);
 #ifdef LRS_PHASE_TIMING
     if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -3168,7 +3310,7 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
 // waves consume the prefetched values, do the arithmetic in registers -- `entry`'s, in its order
 // -- and then issue their stores in one run: no scalar load, no load and no wait for a store's
 // acknowledgement behind the first store of a row within the prefetch window.
-template <int G, int E, int NO, bool PLAIN = false>
+template <int G, int E, int NO, bool PLAIN = false, bool TS = false>
 __global__ void __launch_bounds__(kLatNT) k_lat_b(
     int n, int ld, long foff, const int *__restrict__ adj_ptr, const int *__restrict__ adj_low,
     const int *__restrict__ adj_col, const int *__restrict__ adj_slot, double *Rb0, double *Rb1,
@@ -3256,16 +3398,40 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
     if (ctrl_wave) {
         // ---- control wave: line search (ALMLineSearch lorads_alm.c:266-333)
         double sA[7];
-        sum_partials<7>(pa, nblkA, sA);
-        if (nblkB > 0) {
-            double sB[5];
-            sum_partials<5>(pb, nblkB, sB);
+        if (TS && nblkB <= 0) {
+            // the lane that holds total v stores it: no broadcast
+            const int l64 = threadIdx.x & 63;
+            double a[7];
+            presum_partials<7>(pa, nblkA, a);
+            const double t = wave_tsum<7>(a, l64);
+            if (tsum_owner<7>(l64)) red[tsum_index<7>(l64)] = t;
 #pragma unroll
-            for (int q = 0; q < 5; ++q) sA[2 + q] += sB[q];
-        }
-        if ((threadIdx.x & 63) == 0) {
+            for (int v = 0; v < 7; ++v) sA[v] = t;   // (the stamp's dependence below)
+        } else {
+            if constexpr (TS) {
+                // A's seven and G's five in one pass, through red[0..12)
+                double a[12];
+                presum_partials<7>(pa, nblkA, a);
+                presum_partials<5>(pb, nblkB, a + 7);
+                wave_tsum_to<12>(a, threadIdx.x & 63, red);
+                __builtin_amdgcn_wave_barrier();
 #pragma unroll
-            for (int v = 0; v < 7; ++v) red[v] = sA[v];
+                for (int v = 0; v < 7; ++v) sA[v] = red[v];
+#pragma unroll
+                for (int q = 0; q < 5; ++q) sA[2 + q] += red[7 + q];
+            } else {
+                sum_partials<7>(pa, nblkA, sA);
+                if (nblkB > 0) {
+                    double sB[5];
+                    sum_partials<5>(pb, nblkB, sB);
+#pragma unroll
+                    for (int q = 0; q < 5; ++q) sA[2 + q] += sB[q];
+                }
+            }
+            if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+                for (int v = 0; v < 7; ++v) red[v] = sA[v];
+            }
         }
         __builtin_amdgcn_wave_barrier();
 #ifdef LRS_PHASE_TIMING
@@ -3362,7 +3528,9 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
         pPart = held_gs((double *)partC + (pblk_off + (int)blockIdx.x));
         pLs = held_gs((double *)ls_cur);
         wls = held_s(pblk_off | (int)blockIdx.x);   // 0: the block that publishes the line search
-        nwh = held_s(nwv);
+        // TS, kLatZeroBit beside the wave count (one scalar register for both): this wave's
+        // accumulators stay +0.0 -- the control wave has no row
+        nwh = held_s(nwv | (TS && ctrl_wave ? kLatZeroBit : 0));
     }
     __syncthreads();
     LRS_TS(2, 2);
@@ -3639,9 +3807,10 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
     LRS_TS(2, 3);
     if constexpr (PLAIN) {
         const int tid = held((int)threadIdx.x);   // (formed again here: the prologue's lane ids need not stay live)
-        write_partials_nw_to<10>(acc, write_partials_dst<10>(pPart, 0, tid), nwh, tid);
+        write_partials_nw_to<10>(acc, write_partials_dst<10>(pPart, 0, tid), TS ? nwh & (kLatZeroBit - 1) : nwh, tid,
+                                 TS, TS && (nwh & kLatZeroBit) != 0);
     }
-    else write_partials_nw<10>(acc, partC, pblk_off + blockIdx.x, nwv);
+    else write_partials_nw<10>(acc, partC, pblk_off + blockIdx.x, nwv, TS);
     LRS_TS_END(2, 4);
 #ifdef LRS_PHASE_TIMING
     if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -3657,7 +3826,7 @@ __global__ void __launch_bounds__(kRowBlock) k_lat_f(
     int ld, int w, long foff, const int *__restrict__ adj_ptr, const int *__restrict__ drb, int per,
     const double *__restrict__ gl, const double *__restrict__ Dall, double *G0, double *G1, double *s0, double *y0,
     double *s1, double *y1, const double *__restrict__ ctrl, const double *__restrict__ ls_cur, int L,
-    double *__restrict__ partC, int pblk_off, double *CRb, const double *__restrict__ CDb) {
+    double *__restrict__ partC, int pblk_off, double *CRb, const double *__restrict__ CDb, int ts) {
     if (ctrl[C_ACT2] == 0.0 || ls_cur[LS_FLAG] != 0.0) return;
     const int gcur = (int)ctrl[C_GCUR], h = (int)ctrl[C_HEAD];
     const double *__restrict__ D = Dall + foff;
@@ -3703,7 +3872,7 @@ __global__ void __launch_bounds__(kRowBlock) k_lat_f(
             acc[8] = yov * yv;
         }
     }
-    write_partials<10, kRowBlock>(acc, partC, pblk_off + blockIdx.x);
+    write_partials<10, kRowBlock>(acc, partC, pblk_off + blockIdx.x, ts != 0);
 }
 
 // ------------------------------------------------------------------------
@@ -5425,6 +5594,84 @@ int mfma_f64_probe(hipStream_t st, int wps, int chains, double *tflops, double *
 }
 int mfma_f64_peak(hipStream_t st, double *tflops) { return mfma_f64_probe(st, 2, 8, tflops, nullptr, nullptr); }
 
+// wave_tsum against wave_sum on the caller's inputs, in the latency kernels' two forms.
+// form 0 (one wave), the control-wave prologue: part[v][b], b < n producer blocks, through
+// load_partials, then sum_partials (ref) and tsum_partials (out).  form 1 (n waves), the block
+// tail: thread t's accumulators in[v][t] through write_partials_nw_to without (ref) and with
+// (out) wave_tsum.  ref / out: value v at [v * kMaxPartialBlocks], as a partials array.
+template <int NV>
+__global__ void __launch_bounds__(kLatNT) k_tsum_probe(int form, int n, const double *__restrict__ in,
+                                                       double *__restrict__ ref, double *__restrict__ out) {
+    __shared__ double sred[NV];
+    if (form == 0) {
+        double x[kLatQ][NV], s[NV], t[NV];
+        load_partials<NV>(in, n, x);
+        sum_partials<NV>(x, n, s);
+        tsum_partials<NV>(x, n, sred, t);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                ref[v * kMaxPartialBlocks] = s[v];
+                out[v * kMaxPartialBlocks] = t[v];
+            }
+        }
+    } else {
+        double acc[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) acc[v] = in[v * kLatNT + threadIdx.x];
+        write_partials_nw_to<NV>(acc, write_partials_dst<NV>(ref, 0), n, threadIdx.x, false);
+        __syncthreads();   // (the two calls share the LDS array)
+        write_partials_nw_to<NV>(acc, write_partials_dst<NV>(out, 0), n, threadIdx.x, true);
+    }
+}
+// in: form 0 [nv][n] (1 <= n <= kLatMaxPartials blocks), form 1 [nv][64 n] (1 <= n <= 8 waves);
+// ref, out: [nv] on the host.  1 <= nv <= 16.
+int wave_tsum_probe(hipStream_t st, int form, int nv, int n, const double *in, double *ref, double *out) {
+    if (form < 0 || form > 1 || nv < 1 || nv > 16 || n < 1 || n > (form == 0 ? kLatMaxPartials : kLatNT / 64)) {
+        snprintf(g_err, sizeof(g_err), "wave_tsum_probe: form %d nv %d n %d out of range", form, nv, n);
+        return -1;
+    }
+    static_assert(kMaxPartialBlocks >= kLatNT && kMaxPartialBlocks >= kLatMaxPartials, "probe strides");
+    const size_t len = (size_t)16 * kMaxPartialBlocks;
+    const int cols = form == 0 ? n : 64 * n, stride = form == 0 ? kMaxPartialBlocks : kLatNT;
+    std::vector<double> h(len, 0.0);
+    for (int v = 0; v < nv; ++v)
+        for (int q = 0; q < cols; ++q) h[(size_t)v * stride + q] = in[(size_t)v * cols + q];
+    double *d = nullptr;
+    if (hipMalloc((void **)&d, 3 * len * sizeof(double)) != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "wave_tsum_probe: hipMalloc");
+        return -1;
+    }
+    double *dref = d + len, *dout = d + 2 * len;
+    hipError_t e = hipMemcpyAsync(d, h.data(), len * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dref, 0xFF, 2 * len * sizeof(double), st);
+    if (e == hipSuccess) {
+        const dim3 blk(form == 0 ? 64 : 64 * n);
+        switch (nv) {
+#define LRS_TSUM_PROBE(NV_) \
+    case NV_: hipLaunchKernelGGL(k_tsum_probe<NV_>, dim3(1), blk, 0, st, form, n, d, dref, dout); break;
+            LRS_TSUM_PROBE(1) LRS_TSUM_PROBE(2) LRS_TSUM_PROBE(3) LRS_TSUM_PROBE(4) LRS_TSUM_PROBE(5) LRS_TSUM_PROBE(6)
+            LRS_TSUM_PROBE(7) LRS_TSUM_PROBE(8) LRS_TSUM_PROBE(9) LRS_TSUM_PROBE(10) LRS_TSUM_PROBE(11)
+            LRS_TSUM_PROBE(12) LRS_TSUM_PROBE(13) LRS_TSUM_PROBE(14) LRS_TSUM_PROBE(15) LRS_TSUM_PROBE(16)
+#undef LRS_TSUM_PROBE
+        }
+        e = hipGetLastError();
+    }
+    std::vector<double> r(2 * len);
+    if (e == hipSuccess) e = hipMemcpyAsync(r.data(), dref, 2 * len * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (e != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "wave_tsum_probe: %s", hipGetErrorString(e));
+        return -1;
+    }
+    for (int v = 0; v < nv; ++v) {
+        ref[v] = r[(size_t)v * kMaxPartialBlocks];
+        out[v] = r[len + (size_t)v * kMaxPartialBlocks];
+    }
+    return 0;
+}
+
 // ---- dense objective on the FP64 matrix cores.  The reference's dense
 // branches form sym(U V^T) in full (fds_syr2k, LORADSUVt lorads_alg_common.c:72-89) and multiply
 // by a packed C (dataMatDenseMultiRkMat lorads_sdp_data.c:948-973); here C stays a full n x n
@@ -6369,7 +6616,10 @@ static int forced_regime() {
     }
     return v;
 }
-// force: the context's kernel path (lrs_set_kernel_path): >= 2 forces the bandwidth regime
+// force: the context's kernel path (lrs_set_kernel_path): >= 2 forces the bandwidth regime;
+// kPathLatRows: one lane group a row (no teams) in the latency regime's form, so that the latency
+// kernels also take cones whose denser rows would get teams (tests run them on such cones that way)
+constexpr int kPathLatRows = 5;
 // neighbours in flight per lane group in the bandwidth regime's second halves (MODE 2)
 #ifndef LRS_BW_U
 #define LRS_BW_U 1
@@ -6380,7 +6630,7 @@ static StagePlan plan_stage(long rows_threads, int res_small, int res_large, int
     p.T = T;
     const long need = std::max(1L, (rows_threads * T + kRowBlock - 1) / kRowBlock);
     const int cap = std::max(1, kMaxPartialBlocks / std::max(1, K));
-    const int fr = force >= 2 ? 2 : forced_regime();
+    const int fr = force == kPathLatRows ? 1 : force >= 2 ? 2 : forced_regime();
     if (fr == 2) { p.grid = (int)std::max(1L, std::min<long>(std::min<long>(need, res_large), cap)); p.small = false; return p; }
     if (fr == 1) { p.grid = (int)std::max(1L, std::min<long>(need, cap)); p.small = true; return p; }
     if (need <= res_small) { p.grid = (int)std::min<long>(need, cap); p.small = true; }
@@ -6392,7 +6642,7 @@ static StagePlan plan_stage(long rows_threads, int res_small, int res_large, int
 // every row the layout allows (tests run them on short rows that way)
 static int plan_a(const DevCone &c, int K, StagePlan &p, int force, bool sharded) {
     const double deg = c.nown > 0 ? (double)c.P / c.nown : 0.0;    // lower entries per row
-    const int T = team_size(c, deg, 2);
+    const int T = force == kPathLatRows ? 1 : team_size(c, deg, 2);
     const bool wide_rows = (deg / T >= 32.0 || force == 3) && c.E <= 2;   // p.wide below, but for the grid
     const bool fused = a_fused_rows(c, T, wide_rows, sharded);
     LRS_LAYOUT_SWITCH(c.G, c.E, {
@@ -6404,7 +6654,7 @@ static int plan_a(const DevCone &c, int K, StagePlan &p, int force, bool sharded
 }
 static int plan_b(const DevCone &c, int K, StagePlan &p, int force, bool fused) {
     const double deg = c.nown > 0 ? (double)c.adj_nnz / c.nown : 0.0;
-    const int T = team_size(c, deg, 4);
+    const int T = force == kPathLatRows ? 1 : team_size(c, deg, 4);
     const bool wide_rows = (deg / T >= 64.0 || force == 3) && c.E <= 2;   // p.wide below, but for the grid
     LRS_LAYOUT_SWITCH(c.G, c.E, {
         p = plan_stage((long)c.nown * c.G, res_b<GG, EE, 4>(), res_b<GG, EE, 1>(fused && !wide_rows), K, T, force);
@@ -6421,15 +6671,21 @@ template <int GG, int EE>
 static int res_la() {
     static int c = 0;
     static int cp = 0;   // (either instantiation may be the one launched)
-    return std::min(resident_blocks(k_lat_a<GG, EE, kLatNoA>, &c, kLatNT),
-                    resident_blocks(k_lat_a<GG, EE, kLatNoA, true>, &cp, kLatNT));
+    static int ct = 0, cpt = 0;
+    return std::min(std::min(resident_blocks(k_lat_a<GG, EE, kLatNoA>, &c, kLatNT),
+                             resident_blocks(k_lat_a<GG, EE, kLatNoA, true>, &cp, kLatNT)),
+                    std::min(resident_blocks(k_lat_a<GG, EE, kLatNoA, false, true>, &ct, kLatNT),
+                             resident_blocks(k_lat_a<GG, EE, kLatNoA, true, true>, &cpt, kLatNT)));
 }
 template <int GG, int EE>
 static int res_lb() {
     static int c = 0;
     static int cp = 0;
-    return std::min(resident_blocks(k_lat_b<GG, EE, kLatNoB>, &c, kLatNT),
-                    resident_blocks(k_lat_b<GG, EE, kLatNoB, true>, &cp, kLatNT));
+    static int ct = 0, cpt = 0;
+    return std::min(std::min(resident_blocks(k_lat_b<GG, EE, kLatNoB>, &c, kLatNT),
+                             resident_blocks(k_lat_b<GG, EE, kLatNoB, true>, &cp, kLatNT)),
+                    std::min(resident_blocks(k_lat_b<GG, EE, kLatNoB, false, true>, &ct, kLatNT),
+                             resident_blocks(k_lat_b<GG, EE, kLatNoB, true, true>, &cpt, kLatNT)));
 }
 static bool lat_disabled() {
     static int v = -1;
@@ -6481,6 +6737,12 @@ static bool lat_plain(const DevProblem &P, const DevCone &c, const LatPlan &lp) 
     const char *e = getenv("LRS_LAT_PLAIN");
     if (e && e[0] == '0') return false;
     return c.plain && lp.sa == 0 && lp.sb == 0 && lp.nf == 0 && c.dra_h.empty() && c.drb_h.empty() && !P.ndense;
+}
+// The latency kernels' wave sums by wave_tsum (the transposed butterfly; the same bits).
+// LRS_LAT_TSUM=0 (read per enqueue, as LRS_LAT_PLAIN: tests/test_gpu_lat_tsum.py): one wave_sum a value.
+static bool lat_tsum() {
+    const char *e = getenv("LRS_LAT_TSUM");
+    return !(e && e[0] == '0');
 }
 // LRS_LAT_ROWWAVES = 1..7 forces the row waves per latency block (0: chosen per launch)
 static int lat_forced_waves() {
@@ -6656,7 +6918,7 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
     // latency regime: every launch of both stages on the k_lat kernels, or none
     LatPlan lg[kMaxCones];
     const int ngd = P.ndense ? dense_cd_blocks(P) : 0;   // dense objective: C D's partial blocks
-    bool lat = !sh && !split && !multi_path(P);
+    bool lat = !sh && !split && (multi_path(P) == 0 || multi_path(P) == kPathLatRows);
     int nla = 0, nlb = 0, nlf = 0;
     for (int k = 0; k < KL && lat; ++k) {
         lg[k] = lat_plan(cone_of(k), pa[k], pb[k]);
@@ -6690,6 +6952,8 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
     P.last_path = lat ? 0 : 1;
     P.last_tiles = 0;
     P.last_plain = lat ? 1 : 0;
+    const bool tsum = lat_tsum();
+    P.last_tsum = (lat && tsum) ? 1 : 0;
     for (int k = 0; k < KL && lat; ++k)
         if (!lat_plain(P, cone_of(k), lg[k])) P.last_plain = 0;
     for (int k = 0; k < KL; ++k)
@@ -6757,8 +7021,8 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
                        W.uvt2, W.par, ctrl_prev, ctrl_cur, ls_prev, inC, nC, W.part, off, pa[k].T, gwide, c.row0, \
                        pstr)
         if (lat) {
-#define LRS_LAT_A(PL_)                                                                                         \
-    hipLaunchKernelGGL((k_lat_a<GG, EE, kLatNoA, PL_>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown, c.ld, c.foff,   \
+#define LRS_LAT_A(PL_, TS_)                                                                                    \
+    hipLaunchKernelGGL((k_lat_a<GG, EE, kLatNoA, PL_, TS_>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown, c.ld, c.foff,   \
                        c.adj_ptr, c.adj_low, c.adj_col, c.adj_slot, P.Cw, W.R, W.R2, W.D, W.G[0], W.G[1], W.ls[0], \
                        W.ly[0], W.ls[1], W.ly[1], W.uvt0, W.uvt1, P.loc_ptr, P.loc_con, P.loc_w,                 \
                        reinterpret_cast<const double2 *>(P.loc1), P.b, W.cvs, W.lam, W.rec, k == 0 ? 1 : 0, P.mg,   \
@@ -6767,8 +7031,10 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
                        c.dra)
             const bool plain = lat_plain(P, c, lg[k]);
             LRS_LAYOUT_SWITCH(c.G, c.E, {
-                if (plain) LRS_LAT_A(true);
-                else LRS_LAT_A(false);
+                if (plain && tsum) LRS_LAT_A(true, true);
+                else if (plain) LRS_LAT_A(true, false);
+                else if (tsum) LRS_LAT_A(false, true);
+                else LRS_LAT_A(false, false);
             });
 #undef LRS_LAT_A
         } else {
@@ -6863,8 +7129,8 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
                        (MM) != 2 && k == 0 ? a.hmirror : nullptr, a.seq, P.ndense ? W.CR : nullptr, W.CD)
         const bool small = pb[k].small;
         if (lat) {
-#define LRS_LAT_B(PL_)                                                                                         \
-    hipLaunchKernelGGL((k_lat_b<GG, EE, kLatNoB, PL_>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown, c.ld, c.foff,   \
+#define LRS_LAT_B(PL_, TS_)                                                                                    \
+    hipLaunchKernelGGL((k_lat_b<GG, EE, kLatNoB, PL_, TS_>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown, c.ld, c.foff,   \
                        c.adj_ptr, c.adj_low, c.adj_col, c.adj_slot, W.R, W.R2, W.D, W.G[0], W.G[1], W.ls[0],       \
                        W.ly[0], W.ls[1], W.ly[1], W.uvt2, P.Craw, P.slot_ptr, P.slot_con, P.slot_a,               \
                        reinterpret_cast<const double2 *>(P.slot1), W.rec, P.loc_ptr, P.loc_con, P.loc_w,           \
@@ -6874,8 +7140,10 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
                        P.ndense ? W.CR : nullptr, W.CD)
             const bool plain = lat_plain(P, c, lg[k]);
             LRS_LAYOUT_SWITCH(c.G, c.E, {
-                if (plain) LRS_LAT_B(true);
-                else LRS_LAT_B(false);
+                if (plain && tsum) LRS_LAT_B(true, true);
+                else if (plain) LRS_LAT_B(true, false);
+                else if (tsum) LRS_LAT_B(false, true);
+                else LRS_LAT_B(false, false);
             });
 #undef LRS_LAT_B
             glo += (long)lg[k].sb * c.ld;
@@ -6905,7 +7173,8 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
         if (lg[k].nf > 0) {
             hipLaunchKernelGGL(k_lat_f, dim3(lg[k].nf), dim3(kRowBlock), 0, st, c.ld, c.G * c.E, c.foff, c.adj_ptr,
                                c.drb, ((lg[k].nt - 64) / c.G) * kSliceB, W.gl + glo, W.D, W.G[0], W.G[1], W.ls[0], W.ly[0],
-                               W.ls[1], W.ly[1], ctrl_cur, ls_cur, L, W.partC, off, P.ndense ? W.CR : nullptr, W.CD);
+                               W.ls[1], W.ly[1], ctrl_cur, ls_cur, L, W.partC, off, P.ndense ? W.CR : nullptr, W.CD,
+                               tsum ? 1 : 0);
             LRS_CHECK_LAUNCH();
         }
         glo += (long)lg[k].sb * c.ld;

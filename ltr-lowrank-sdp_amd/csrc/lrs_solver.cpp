@@ -2930,9 +2930,9 @@ int lrs_ctx_create(int device, lrs_ctx **out) {
 
 int lrs_set_kernel_path(lrs_ctx *c, int path) {
     LRS_NEED_LOADED(c);
-    if (path < 0 || path > 4) {
-        set_err("kernel path %d: expected 0 (auto), 1 (general), 2 (general, bandwidth regime), 3 (+ long-row kernels) "
-                "or 4 (the single-workgroup inner loop where it fits)", path);
+    if (path < 0 || path > 5) {
+        set_err("kernel path %d: expected 0 (auto), 1 (general), 2 (general, bandwidth regime), 3 (+ long-row kernels), "
+                "4 (the single-workgroup inner loop where it fits) or 5 (auto without teams)", path);
         return -1;
     }
     if (c->dp.no_lat != path) {
@@ -2959,6 +2959,13 @@ int lrs_lat_plain_used(lrs_ctx *c, int *used) {
     LRS_NEED_CTX(c);
     LRS_NEED_ARG(used);
     *used = (c->loaded && c->dp.last_path == 0) ? c->dp.last_plain : 0;
+    return 0;
+}
+
+int lrs_lat_tsum_used(lrs_ctx *c, int *used) {
+    LRS_NEED_CTX(c);
+    LRS_NEED_ARG(used);
+    *used = (c->loaded && c->dp.last_path == 0) ? c->dp.last_tsum : 0;
     return 0;
 }
 
@@ -4120,6 +4127,13 @@ int lrs_mfma_f64_probe(lrs_ctx *c, int waves_per_simd, int chains, double *tflop
     if (!c || !tflops) { set_err("mfma_f64_probe: null argument"); return -1; }
     bind(c);
     OPC(mfma_f64_probe(c->st, waves_per_simd, chains, tflops, mhz, cycles_per_mfma));
+    return 0;
+}
+
+int lrs_wave_tsum_probe(lrs_ctx *c, int form, int nv, int n, const double *in, double *ref, double *out) {
+    if (!c || !in || !ref || !out) { set_err("wave_tsum_probe: null argument"); return -1; }
+    bind(c);
+    OPC(wave_tsum_probe(c->st, form, nv, n, in, ref, out));
     return 0;
 }
 

@@ -123,6 +123,8 @@ def load_library(path=None):
         "lrs_op_dual_infeasibility": (C.c_int, [vp, dp, dp]),
         "lrs_get_kernel_path": (C.c_int, [vp, ip]),
         "lrs_lat_plain_used": (C.c_int, [vp, ip]),
+        "lrs_lat_tsum_used": (C.c_int, [vp, ip]),
+        "lrs_wave_tsum_probe": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp]),
         "lrs_stage_bytes": (C.c_int, [vp, dp]),
         "lrs_tile_info": (C.c_int, [vp, ip, ip]),
         "lrs_tile_used": (C.c_int, [vp, ip]),
@@ -581,7 +583,8 @@ class Solver:
         return list(v)
 
     def set_kernel_path(self, path):
-        """0 = automatic (latency-regime kernels where they apply), 1 = general row kernels."""
+        """0 = automatic (latency-regime kernels where they apply), 1 = general row kernels, 5 =
+        automatic without lane-group teams (the latency kernels on cones with denser rows too)."""
         self._check(self.lib.lrs_set_kernel_path(self.ctx, int(path)), "set_kernel_path")
 
     def dual_infeasibility(self):
@@ -602,6 +605,27 @@ class Solver:
         v = C.c_int(0)
         self._check(self.lib.lrs_lat_plain_used(self.ctx, C.byref(v)), "lat_plain_used")
         return bool(v.value)
+
+    def lat_tsum_used(self):
+        """True when the last enqueued ALM iteration ran the latency kernels with their wave sums as
+        transposed butterflies (LRS_LAT_TSUM=0: one wave sum a value)."""
+        v = C.c_int(0)
+        self._check(self.lib.lrs_lat_tsum_used(self.ctx, C.byref(v)), "lat_tsum_used")
+        return bool(v.value)
+
+    def wave_tsum_probe(self, form, x):
+        """The latency kernels' wave sums of x in both forms, (ref, new), each [nv]
+        (lrs_wave_tsum_probe).  form 0: x[nv][nblk], the control wave's sum over nblk producer
+        blocks' partials.  form 1: x[nv][64 nw], the block tail over nw waves' accumulators."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        nv, cols = x.shape
+        n = cols if form == 0 else cols // 64
+        if form != 0 and cols != 64 * n:
+            raise ValueError("form 1 takes 64 accumulators a wave")
+        ref, out = np.empty(nv), np.empty(nv)
+        self._check(self.lib.lrs_wave_tsum_probe(self.ctx, int(form), nv, n, _dptr(x), _dptr(ref), _dptr(out)),
+                    "wave_tsum_probe")
+        return ref, out
 
     def time_stages(self, reps=200):
         """Per-launch ms of the split-iteration stages [A, G, B] (back-to-back relaunches)."""
