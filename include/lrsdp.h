@@ -193,8 +193,18 @@ int lrs_solve(lrs_ctx *ctx, const lrs_params *p, lrs_result *res);
  * workgroup) stops launching on its own: the members currently in that phase meet, and one
  * launch per kernel instantiation runs all of them, one block each -- each block computes bit for
  * bit what the instance's own launch computes.  Every other instance (LP blocks, dense or rank-one
- * coefficients, lbfgsListLength != 2, multi-launch kernel paths, one workgroup per cone) and every
- * other phase (ADMM, the dual infeasibility) runs unchanged on the context's own stream.
+ * coefficients, lbfgsListLength != 2, multi-launch kernel paths, one workgroup per cone) runs that
+ * phase unchanged on the context's own stream.
+ * The ADMM phase has a second, independent meeting: a member inside that phase (the first pass or a
+ * reoptimisation's) whose iteration is wholly the one-workgroup form -- every cone on the
+ * single-workgroup half-step with one kernel variant, no constraint across cones, the one-launch
+ * evaluation; no LP block, no dense or rank-one constraint matrices -- files its iteration and
+ * parks; one round runs the parked members' side-0 half-steps, their side-1 half-steps and their
+ * evaluations in shared launches, a block a cone, each bit for bit the member's own launch.  A
+ * member in one phase never waits for members in the other.  The dual update, the rank oracle's
+ * Gram, the first evaluation of a phase, every member that does not qualify and the dual
+ * infeasibility stay on the context's own stream.  LRS_BATCH_ADMM=0 in the environment (read at
+ * each lrs_solve_batch) keeps every member's ADMM phase on its own stream.
  * lrs_solve_batch: n contexts (distinct, same device, unsharded, each with a problem loaded;
  * n <= LRS_BATCH_MAX), params[n] or one shared set (nparams = 1 or n), res[n], rc[n]: each
  * instance's own return code and, on failure, its message through lrs_batch_error(b, i).  Returns
@@ -211,7 +221,12 @@ int lrs_solve(lrs_ctx *ctx, const lrs_params *p, lrs_result *res);
  * calls served by combined launches; single-workgroup inner-loop calls that launched alone (the
  * one-workgroup-per-cone members').
  * lrs_batch_round_widths: out[w] (w < cap) = rounds of the last call that ran w blocks; *rounds
- * their number (each may be NULL). */
+ * their number (each may be NULL).  Both count the ALM meeting only.
+ * lrs_batch_admm_stats, the ADMM meeting's of the last lrs_solve_batch (each may be NULL): combined
+ * ADMM launches; the widest round in members; ADMM iterations served by rounds; ADMM iterations
+ * that members ran on their own stream.  lrs_batch_admm_round_widths: as lrs_batch_round_widths,
+ * w in members.  lrs_batch_admm_shape: the most kernel variants of the half-step launched in one
+ * round, and the most blocks (cones) in one half-step launch. */
 #define LRS_BATCH_MAX 256
 typedef struct lrs_batch lrs_batch;
 int lrs_batch_create(lrs_batch **out);
@@ -221,6 +236,21 @@ int lrs_solve_batch(lrs_batch *b, lrs_ctx **ctxs, int n, const lrs_params *param
 const char *lrs_batch_error(lrs_batch *b, int i);
 int lrs_batch_stats(lrs_batch *b, long *launches, int *widest, long *served, long *alone);
 int lrs_batch_round_widths(lrs_batch *b, long *out, int cap, long *rounds);
+int lrs_batch_admm_stats(lrs_batch *b, long *launches, int *widest, long *served, long *alone);
+int lrs_batch_admm_round_widths(lrs_batch *b, long *out, int cap, long *rounds);
+int lrs_batch_admm_shape(lrs_batch *b, int *variants, int *blocks);
+/* Operator-level access to one ADMM round (tests, as lrs_op_admm_half is to one half-step): for n
+ * contexts with solver state, each after lrs_op_admm_constr and each qualifying for the ADMM
+ * meeting (else refused), the shared launches of one iteration -- side 0 of every cone, side 1 of
+ * every cone, the evaluation (R = (U + V) / 2, CVS = A(R R^T)) -- at rho[i], cg_tol[i], cg_maxit.
+ * No dual update.  lrs_op_admm_rhs: the right-hand side the last half-step of `cone` left
+ * (column-major n_k x r_k, as lrs_op_admm_half's rhs). */
+int lrs_op_admm_round(lrs_batch *b, lrs_ctx **ctxs, int n, const double *rho, const double *cg_tol, int cg_maxit);
+int lrs_op_admm_rhs(lrs_ctx *ctx, int cone, double *rhs);
+/* How the context's ADMM iteration runs at its current ranks (each may be NULL): the cones whose
+ * half-step is the single-workgroup kernel, and whether the whole iteration is the
+ * one-workgroup form that the ADMM meeting of a batch combines. */
+int lrs_admm_form(lrs_ctx *ctx, int *small_cg_cones, int *round_form);
 /* trajectory (phase 1 then phase 2) after lrs_solve: curr and oracle ranks */
 int lrs_trajectory(lrs_ctx *ctx, int phase, int *curr_rank, int *oracle_rank, int cap);
 /* JSON like lorads_logging.c:618-712 */

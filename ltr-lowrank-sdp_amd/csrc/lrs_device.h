@@ -453,6 +453,25 @@ struct SmallBatchMember {
 int small_batch_create(SmallBatch **out, int cap);
 void small_batch_destroy(SmallBatch *b);
 int launch_small_alm_batch(SmallBatch *b, const SmallBatchMember *mem, int n, int *launches);
+// The ADMM iterations of many contexts at once (the batch's ADMM rendezvous): member i's two
+// half-step launches and its evaluation launch as admm_update_var / admm_eval form them
+// (small_admm_fits: every cone on k_small_cg with one variant, k_small_eval), combined into a
+// side-0 and a side-1 launch per kernel variant and one evaluation launch, a block a cone, each
+// bitwise the member's own.  host_tot receives the member's evaluation sums ([K][4], three used),
+// host_cg its W.cgc[CG_TOTAL].  Returns when the round's streams (its own, not the ALM round's)
+// have drained; the members' streams must be idle.  *launches is advanced by the launches made.
+struct SmallAdmmMember {
+    const DevProblem *P;
+    DevWork *W;
+    double rho, tol;
+    int maxit;
+    double *host_tot, *host_cg;
+};
+bool small_admm_fits(const DevProblem &P);
+int launch_small_admm_batch(SmallBatch *b, const SmallAdmmMember *mem, int n, int *launches);
+// since small_admm_batch_reset: the most kernel variants in one round, the most blocks in one launch
+void small_admm_batch_shape(const SmallBatch *b, int *variants, int *blocks);
+void small_admm_batch_reset(SmallBatch *b);
 
 // ---- device-resident CG (lrs_kernels.hip "Device-resident CG") ----
 enum CgIdx { CG_ACTIVE = 0, CG_ITERS, CG_BNORM, CG_RR, CG_QTR0, CG_QTR1, CG_TOTAL, CG_N = 8 };

@@ -8116,6 +8116,8 @@ int launch_small_alm(const DevProblem &P, DevWork &W, const double *ctrl_in, dou
 
 // ---- batched launch (lrs_solve_batch): one round of the rendezvous ----
 constexpr int kSmallBatchStreams = 4;
+struct SmallCgArgs;
+struct SmallEvalEntry;
 struct SmallBatch {
     int cap = 0;
     hipStream_t st[kSmallBatchStreams] = {};
@@ -8123,6 +8125,15 @@ struct SmallBatch {
     double *hctl = nullptr, *dctl = nullptr;      // the members' final control blocks ([cap][64])
     std::vector<int> order, ld;
     std::vector<size_t> lds;
+    // the ADMM round's own (launch_small_admm_batch; allocated at its first round): an ALM round
+    // and an ADMM round may run at the same time, so they share no stream, table or mirror
+    hipStream_t ast[kSmallBatchStreams] = {};
+    hipEvent_t aev[kSmallBatchStreams] = {};
+    SmallCgArgs *acg_h = nullptr, *acg_d = nullptr;       // half-step entries, per group [side 0][side 1]
+    SmallEvalEntry *aev_h = nullptr, *aev_d = nullptr;    // evaluation entries
+    double *amir_h = nullptr, *amir_d = nullptr;          // [block][4] evaluation sums, CG totals
+    std::vector<int> aorder, avar, aev0;
+    int a_variants = 0, a_blocks = 0;   // most kernel variants in a round, most blocks in a launch
 };
 void small_batch_destroy(SmallBatch *b) {
     if (!b) return;
@@ -8132,6 +8143,16 @@ void small_batch_destroy(SmallBatch *b) {
     if (b->hctl) (void)hipHostFree(b->hctl);
     if (b->dtab) (void)hipFree(b->dtab);
     if (b->dctl) (void)hipFree(b->dctl);
+    for (hipStream_t s : b->ast)
+        if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : b->aev)
+        if (e) (void)hipEventDestroy(e);
+    if (b->acg_h) (void)hipHostFree(b->acg_h);
+    if (b->aev_h) (void)hipHostFree(b->aev_h);
+    if (b->amir_h) (void)hipHostFree(b->amir_h);
+    if (b->acg_d) (void)hipFree(b->acg_d);
+    if (b->aev_d) (void)hipFree(b->aev_d);
+    if (b->amir_d) (void)hipFree(b->amir_d);
     delete b;
 }
 int small_batch_create(SmallBatch **out, int cap) {
@@ -8539,9 +8560,11 @@ __device__ __forceinline__ void sc_row_apply(int e0, int e1, const int *cadj, co
     }
 }
 
-template <int EL, int RPG>
-__global__ void __launch_bounds__(kScT) k_small_cg(SmallCgBatch Bt) {
-    const SmallCgArgs &A = Bt.a[blockIdx.x];
+// The half-step of one block.  ARGS is a reference to the block's SmallCgArgs: the solo kernel's
+// entry of its argument segment, or (TAB, k_small_cg_tab) the block's entry of a round's table in
+// the constant address space -- either way uniform scalar loads, never a private copy.
+template <int EL, int RPG, bool TAB, typename ARGS>
+__device__ __forceinline__ void small_cg_body(ARGS A) {
     extern __shared__ double smem[];
     const int n = A.n, r = A.r, rS = A.rS;
     double *Ys = smem;                         // [n][rS] the fixed factor
@@ -8887,7 +8910,8 @@ __global__ void __launch_bounds__(kScT) k_small_cg(SmallCgBatch Bt) {
             // a batch launch (one block per cone, launch_small_cg_batch) has no single count to report:
             // CG_ITERS is the one-cone launch's (lrs_op_admm_half reads it); every launch adds its
             // cones' counts to CG_TOTAL, the one the ADMM log and lrs_result use
-            if (gridDim.x == 1) A.cgc[CG_ITERS] = iters;
+            // (a table block never reports one: its launch holds other members' cones)
+            if (!TAB && gridDim.x == 1) A.cgc[CG_ITERS] = iters;
             atomicAdd(A.cgc + CG_TOTAL, (double)iters);   // several cones' blocks: integers, exact in any order
 #ifdef LRS_PHASE_TIMING
             g_phase[1][14] += iters;
@@ -8918,6 +8942,20 @@ __global__ void __launch_bounds__(kScT) k_small_cg(SmallCgBatch Bt) {
     }
     LRS_SC_T(12);
 #undef LRS_SC_T
+}
+template <int EL, int RPG>
+__global__ void __launch_bounds__(kScT) k_small_cg(SmallCgBatch Bt) {
+    small_cg_body<EL, RPG, false, const SmallCgArgs &>(Bt.a[blockIdx.x]);
+}
+// One side of one round of a batched solve's ADMM phase (launch_small_admm_batch, DESIGN.md
+// §4.11): block b runs tab[b], a cone of some member, through the body above.  The table is
+// written before the launch and by no kernel, so it is read through the constant address space
+// like k_small_alm_batch's.  No block waits on another: a launch may hold more blocks than the
+// chip has CUs, in any order.  Each block adds its iterations to its own member's cgc[CG_TOTAL].
+template <int EL, int RPG>
+__global__ void __launch_bounds__(kScT) k_small_cg_tab(const SmallCgArgs *__restrict__ tab) {
+    typedef const __attribute__((address_space(4))) SmallCgArgs CArgs;
+    small_cg_body<EL, RPG, true, CArgs &>(*(CArgs *)(unsigned long long)(tab + blockIdx.x));
 }
 
 // The instantiated (elements per lane, rows per group) for a cone, 0 if none: EL 1 with up to
@@ -9065,10 +9103,25 @@ struct SmallEvalArgs {
     const double *U, *V, *b, *lam, *Craw;
     double *R, *cvs, *cvc, *out;   // out: [K][4]
 };
+// One block of a round's evaluation (k_small_eval_tab): what the solo block takes from
+// blockIdx.x (k: the cone within its member, which fixes the cvc row and the out[4k..] slot) and
+// from the shared part of SmallEvalArgs, per block.  cgc / mir: the member's device-counted CG
+// iterations and the round's mirror ([block][4]: the block's three sums, and from the k = 0
+// block the member's cgc[CG_TOTAL]), so the host fetches a round's results in one copy.
+struct SmallEvalEntry {
+    SmallEvalCone c;
+    int k, m;
+    const double *U, *V, *b, *lam, *Craw, *cgc;
+    double *R, *cvs, *cvc, *out, *mir;
+};
 constexpr int kSeT = 256;
-__global__ void __launch_bounds__(kSeT) k_small_eval(SmallEvalArgs A) {
-    const int k = blockIdx.x, tid = threadIdx.x;
-    const SmallEvalCone &C = A.c[k];
+// The evaluation of one cone.  CONE is a reference to the block's SmallEvalCone (argument
+// segment or table entry in the constant address space); the rest by value, loaded by the caller.
+template <typename CONE>
+__device__ __forceinline__ void small_eval_body(CONE C, const int k, const int m, const double *gU, const double *gV,
+                                                const double *gb, const double *glam, const double *gCraw, double *gR,
+                                                double *gcvs, double *gcvc, double (&s3)[3]) {
+    const int tid = threadIdx.x;
     const int n = C.n, r = C.r;
     extern __shared__ __attribute__((aligned(16))) double se[];
     double *Rs = se;                   // [n][r]
@@ -9077,8 +9130,8 @@ __global__ void __launch_bounds__(kSeT) k_small_eval(SmallEvalArgs A) {
     for (int t = tid; t < n * C.ld; t += kSeT) {   // every column of the rows, as k_avg
         const int i = t / C.ld, c = t - i * C.ld;
         const long o = C.foff + t;
-        const double v = (A.U[o] + A.V[o]) / 2;
-        A.R[o] = v;
+        const double v = (gU[o] + gV[o]) / 2;
+        gR[o] = v;
         if (c < r) Rs[(long)i * r + c] = v;
     }
     __syncthreads();
@@ -9102,15 +9155,15 @@ __global__ void __launch_bounds__(kSeT) k_small_eval(SmallEvalArgs A) {
         double v = 0.0;
         for (int e = C.cl_ptr[j]; e < C.cl_ptr[j + 1]; ++e) v += C.ce_w[e] * T[C.ce[e] >> 1];
         const int gi = C.cl_con[j];
-        A.cvs[gi] = v;
-        A.cvc[(long)k * A.m + gi] = v;
-        const double d = A.b[gi] - v;
+        gcvs[gi] = v;
+        gcvc[(long)k * m + gi] = v;
+        const double d = gb[gi] - v;
         acc[0] += d * d;
-        acc[2] += A.b[gi] * A.lam[gi];
+        acc[2] += gb[gi] * glam[gi];
     }
     if (C.cconst) {
         if (tid == 0) {
-            const double a = C.cconst == 2 ? C.calpha : A.Craw[C.cslot];
+            const double a = C.cconst == 2 ? C.calpha : gCraw[C.cslot];
             double t = 0.0;
             for (int c = 0; c < r; ++c) t += cs[c] * cs[c];
             acc[1] = a * t;
@@ -9121,13 +9174,41 @@ __global__ void __launch_bounds__(kSeT) k_small_eval(SmallEvalArgs A) {
                 const int j = C.cc[2 * q], sl = C.cc[2 * q + 1];
                 double d = 0.0;
                 for (int c = 0; c < r; ++c) d += Rs[(long)i * r + c] * Rs[(long)j * r + c];
-                acc[1] += A.Craw[sl] * d;
+                acc[1] += gCraw[sl] * d;
             }
     }
-    double s3[3];
     block_reduce<3, kSeT>(acc, s3);
-    if (tid == 0)
+}
+__global__ void __launch_bounds__(kSeT) k_small_eval(SmallEvalArgs A) {
+    const int k = blockIdx.x;
+    double s3[3];
+    small_eval_body<const SmallEvalCone &>(A.c[k], k, A.m, A.U, A.V, A.b, A.lam, A.Craw, A.R, A.cvs, A.cvc, s3);
+    if (threadIdx.x == 0)
         for (int q = 0; q < 3; ++q) A.out[4 * k + q] = s3[q];
+}
+// The evaluations of every member of a round in one launch: block b takes tab[b] (constant
+// address space, as k_small_cg_tab).  Launched after both sides of every member's half-steps.
+__global__ void __launch_bounds__(kSeT) k_small_eval_tab(const SmallEvalEntry *__restrict__ tab) {
+    typedef const __attribute__((address_space(4))) SmallEvalEntry CEntry;
+    typedef const __attribute__((address_space(4))) SmallEvalCone CCone;
+    CEntry &E = *(CEntry *)(unsigned long long)(tab + blockIdx.x);
+    const int k = E.k;
+    double s3[3];
+    small_eval_body<CCone &>(E.c, k, E.m, E.U, E.V, E.b, E.lam, E.Craw, E.R, E.cvs, E.cvc, s3);
+    if (threadIdx.x == 0) {
+        double *mir = E.mir + 4L * blockIdx.x;
+        for (int q = 0; q < 3; ++q) {
+            E.out[4 * k + q] = s3[q];
+            mir[q] = s3[q];
+        }
+        if (k == 0) mir[3] = E.cgc[CG_TOTAL];
+    }
+}
+static SmallEvalCone small_eval_cone(const DevProblem &P, int k) {
+    const DevCone &c = P.cones[k];
+    return SmallEvalCone{c.n, c.r, c.ld, c.cg_ncs, c.cg_ncl, c.dense_c == 2 ? 2 : c.cg_cconst, c.cg_cslot, c.foff,
+                         P.dense_scale * c.c_alpha, c.cg_cadj_ptr, c.cg_cadj, c.cg_cl_con, c.cg_cl_ptr, c.cg_ce,
+                         c.cg_cc_ptr, c.cg_cc, c.cg_ce_w};
 }
 static size_t small_eval_lds(const DevCone &c) { return ((size_t)c.n * c.r + c.cg_ncs + c.r) * sizeof(double); }
 bool small_eval_fits(const DevProblem &P) {
@@ -9148,16 +9229,210 @@ int launch_small_eval(const DevProblem &P, DevWork &W, const double *U, const do
     SmallEvalArgs A{};
     size_t lds = 0;
     for (int k = 0; k < P.K; ++k) {
-        const DevCone &c = P.cones[k];
-        A.c[k] = SmallEvalCone{c.n, c.r, c.ld, c.cg_ncs, c.cg_ncl, c.dense_c == 2 ? 2 : c.cg_cconst, c.cg_cslot, c.foff,
-                               P.dense_scale * c.c_alpha, c.cg_cadj_ptr, c.cg_cadj, c.cg_cl_con, c.cg_cl_ptr, c.cg_ce,
-                               c.cg_cc_ptr, c.cg_cc, c.cg_ce_w};
-        lds = std::max(lds, small_eval_lds(c));
+        A.c[k] = small_eval_cone(P, k);
+        lds = std::max(lds, small_eval_lds(P.cones[k]));
     }
     A.m = P.m; A.U = U; A.V = V; A.b = P.b; A.lam = W.lam; A.Craw = P.Craw;
     A.R = W.R; A.cvs = W.cvs; A.cvc = W.cvc; A.out = out;
     hipLaunchKernelGGL(k_small_eval, dim3(P.K), dim3(kSeT), lds, st, A);
     LRS_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- batched ADMM iteration (lrs_solve_batch): one round of the ADMM rendezvous ----
+template <int EL, int RPG>
+static int launch_small_cg_tab_t(const SmallCgArgs *tab, int nb, size_t lds, hipStream_t st) {
+    static bool attr = false;
+    if (!attr) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_small_cg_tab<EL, RPG>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kScMaxDynLds) != hipSuccess) {
+            snprintf(g_err, sizeof(g_err), "batched ADMM half-steps: LDS attribute refused");
+            return -1;
+        }
+        attr = true;
+    }
+    hipLaunchKernelGGL((k_small_cg_tab<EL, RPG>), dim3(nb), dim3(kScT), lds, st, tab);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+static int launch_small_cg_tab_v(int v, const SmallCgArgs *tab, int nb, size_t lds, hipStream_t st) {
+    switch (v) {
+    case 1 * 16 + 2: return launch_small_cg_tab_t<1, 2>(tab, nb, lds, st);
+    case 1 * 16 + 4: return launch_small_cg_tab_t<1, 4>(tab, nb, lds, st);
+    case 1 * 16 + 6: return launch_small_cg_tab_t<1, 6>(tab, nb, lds, st);
+    case 1 * 16 + 8: return launch_small_cg_tab_t<1, 8>(tab, nb, lds, st);
+    case 2 * 16 + 2: return launch_small_cg_tab_t<2, 2>(tab, nb, lds, st);
+#if LRS_SC_NT == 1024
+    case 1 * 16 + 3: return launch_small_cg_tab_t<1, 3>(tab, nb, lds, st);
+    case 2 * 16 + 3: return launch_small_cg_tab_t<2, 3>(tab, nb, lds, st);
+#endif
+    case 2 * 16 + 4: return launch_small_cg_tab_t<2, 4>(tab, nb, lds, st);
+    case 2 * 16 + 6: return launch_small_cg_tab_t<2, 6>(tab, nb, lds, st);
+    case 3 * 16 + 2: return launch_small_cg_tab_t<3, 2>(tab, nb, lds, st);
+    case 3 * 16 + 4: return launch_small_cg_tab_t<3, 4>(tab, nb, lds, st);
+    case 4 * 16 + 2: return launch_small_cg_tab_t<4, 2>(tab, nb, lds, st);
+    default:
+        snprintf(g_err, sizeof(g_err), "batched ADMM half-steps: no variant %d", v);
+        return -1;
+    }
+}
+// Whether a context's whole ADMM iteration is the one-workgroup form (a half-step launch a side
+// with a block a cone, and the evaluation launch): what a member of a round must be.
+bool small_admm_fits(const DevProblem &P) {
+    if (P.lp_cone >= 0 || P.ndensea != 0 || P.K < 1 || !small_cg_fits(P, 0)) return false;
+    if (P.K > 1 && !small_cg_batch_fits(P)) return false;
+    return small_eval_fits(P);
+}
+// the round's tables, mirror, streams and events: allocated at the first round
+static int small_admm_alloc(SmallBatch *b) {
+    if (b->acg_h) return 0;
+    const size_t nent = (size_t)b->cap * kSmallMaxWg;
+    bool ok = true;
+    for (hipStream_t &s : b->ast) ok = ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
+    for (hipEvent_t &e : b->aev) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipHostMalloc((void **)&b->acg_h, sizeof(SmallCgArgs) * 2 * nent, 0) == hipSuccess;
+    ok = ok && hipMalloc((void **)&b->acg_d, sizeof(SmallCgArgs) * 2 * nent) == hipSuccess;
+    ok = ok && hipHostMalloc((void **)&b->aev_h, sizeof(SmallEvalEntry) * nent, 0) == hipSuccess;
+    ok = ok && hipMalloc((void **)&b->aev_d, sizeof(SmallEvalEntry) * nent) == hipSuccess;
+    ok = ok && hipHostMalloc((void **)&b->amir_h, sizeof(double) * 4 * nent, 0) == hipSuccess;
+    ok = ok && hipMalloc((void **)&b->amir_d, sizeof(double) * 4 * nent) == hipSuccess;
+    if (!ok) {
+        snprintf(g_err, sizeof(g_err), "batched ADMM iteration: stream or table allocation failed");
+        return -1;
+    }
+    return 0;
+}
+void small_admm_batch_shape(const SmallBatch *b, int *variants, int *blocks) {
+    if (variants) *variants = b->a_variants;
+    if (blocks) *blocks = b->a_blocks;
+}
+void small_admm_batch_reset(SmallBatch *b) { b->a_variants = b->a_blocks = 0; }
+// One round: the n members' ADMM iterations, each as admm_update_var + admm_eval launch it alone
+// (launch_small_cg / launch_small_cg_batch on side 0 then 1, then launch_small_eval), a block a
+// cone.  The half-step entries are grouped by kernel variant (a member's cones share one); a
+// group's table part is [side 0 entries][side 1 entries], uploaded and launched (side 0, then
+// side 1) on one of up to four streams with the group's largest dynamic LDS.  The evaluation of
+// every member is one launch on stream 0 behind an event of each other stream; it also writes
+// each block's sums (and from a member's first block its CG total) into the round's mirror, which
+// one copy brings to the host.  No host wait between the stages.  The caller has made every
+// member's earlier work complete.  Returns after the streams have drained, the members' results
+// in host_tot / host_cg, so the tables and the mirror are free for the next round.
+int launch_small_admm_batch(SmallBatch *b, const SmallAdmmMember *mem, int n, int *launches) {
+    if (n <= 0 || n > b->cap) {
+        snprintf(g_err, sizeof(g_err), "batched ADMM iteration: %d members (capacity %d)", n, b->cap);
+        return -1;
+    }
+    if (small_admm_alloc(b)) return -1;
+    // members in variant order (stable: ascending member index within a variant)
+    std::vector<int> &order = b->aorder, &var = b->avar;
+    order.resize(n); var.resize(n);
+    for (int i = 0; i < n; ++i) {
+        if (!small_admm_fits(*mem[i].P)) {
+            snprintf(g_err, sizeof(g_err), "batched ADMM iteration: member %d is not the one-workgroup form", i);
+            return -1;
+        }
+        var[i] = small_cg_variant(mem[i].P->cones[0]);
+        order[i] = i;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return var[x] < var[y]; });
+    unsigned used = 1u;   // stream 0: the evaluation's
+    auto bail = [&](int rc) {   // nothing may still read the tables when the caller reuses them
+        for (int si = 0; si < kSmallBatchStreams; ++si)
+            if ((used >> si) & 1u) (void)hipStreamSynchronize(b->ast[si]);
+        return rc;
+    };
+    // the evaluation table, in member order of the sort (its blocks' order is immaterial)
+    int nev = 0;
+    size_t ev_lds = 0;
+    std::vector<int> &ev0 = b->aev0;
+    ev0.resize(n);
+    for (int q = 0; q < n; ++q) {
+        const SmallAdmmMember &M = mem[order[q]];
+        const DevProblem &P = *M.P;
+        DevWork &W = *M.W;
+        ev0[q] = nev;
+        for (int k = 0; k < P.K; ++k) {
+            SmallEvalEntry &E = b->aev_h[nev++];
+            E = SmallEvalEntry{};
+            E.c = small_eval_cone(P, k);
+            E.k = k; E.m = P.m;
+            E.U = W.U; E.V = W.V; E.b = P.b; E.lam = W.lam; E.Craw = P.Craw; E.cgc = W.cgc;
+            E.R = W.R; E.cvs = W.cvs; E.cvc = W.cvc; E.out = W.tot; E.mir = b->amir_d;
+            ev_lds = std::max(ev_lds, small_eval_lds(P.cones[k]));
+        }
+    }
+    if (hipMemcpyAsync(b->aev_d, b->aev_h, sizeof(SmallEvalEntry) * nev, hipMemcpyHostToDevice, b->ast[0]) != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "batched ADMM iteration: table upload failed");
+        return bail(-1);
+    }
+    int ngroups = 0, off = 0, nlaunch = 0;
+    for (int q0 = 0; q0 < n;) {
+        int q1 = q0, nb = 0;
+        while (q1 < n && var[order[q1]] == var[order[q0]]) nb += mem[order[q1++]].P->K;
+        SmallCgArgs *h = b->acg_h + off;
+        size_t lds = 0;
+        int e = 0;
+        for (int q = q0; q < q1; ++q) {
+            const SmallAdmmMember &M = mem[order[q]];
+            for (int k = 0; k < M.P->K; ++k, ++e) {
+                for (int side = 0; side < 2; ++side)
+                    small_cg_args(*M.P, *M.W, k, side, M.rho, M.tol, M.maxit, h[side * nb + e]);
+                const SmallCgArgs &A = h[e];
+                lds = std::max(lds, small_cg_lds(A.n, A.rS, A.ncl, A.ncs, A.nce, A.nsc, A.nadj));
+            }
+        }
+        const int si = ngroups % kSmallBatchStreams;
+        hipStream_t st = b->ast[si];
+        used |= 1u << si;
+        SmallCgArgs *d = b->acg_d + off;
+        if (hipMemcpyAsync(d, h, sizeof(SmallCgArgs) * 2 * nb, hipMemcpyHostToDevice, st) != hipSuccess) {
+            snprintf(g_err, sizeof(g_err), "batched ADMM iteration: table upload failed");
+            return bail(-1);
+        }
+        for (int side = 0; side < 2; ++side)
+            if (launch_small_cg_tab_v(var[order[q0]], d + side * nb, nb, lds, st)) return bail(-1);
+        nlaunch += 2;
+        b->a_blocks = std::max(b->a_blocks, nb);
+        off += 2 * nb;
+        ngroups++;
+        q0 = q1;
+    }
+    b->a_variants = std::max(b->a_variants, ngroups);
+    // the evaluation behind every group's side 1
+    for (int si = 1; si < kSmallBatchStreams; ++si)
+        if ((used >> si) & 1u) {
+            if (hipEventRecord(b->aev[si], b->ast[si]) != hipSuccess ||
+                hipStreamWaitEvent(b->ast[0], b->aev[si], 0) != hipSuccess) {
+                snprintf(g_err, sizeof(g_err), "batched ADMM iteration: event failed");
+                return bail(-1);
+            }
+        }
+    hipLaunchKernelGGL(k_small_eval_tab, dim3(nev), dim3(kSeT), ev_lds, b->ast[0], b->aev_d);
+    if (hipGetLastError() != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "batched ADMM iteration: evaluation launch failed");
+        return bail(-1);
+    }
+    nlaunch++;
+    if (hipMemcpyAsync(b->amir_h, b->amir_d, sizeof(double) * 4 * nev, hipMemcpyDeviceToHost, b->ast[0]) != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "batched ADMM iteration: result copy failed");
+        return bail(-1);
+    }
+    for (int si = 0; si < kSmallBatchStreams; ++si)
+        if ((used >> si) & 1u) {
+            const hipError_t e = hipStreamSynchronize(b->ast[si]);
+            if (e != hipSuccess) {
+                snprintf(g_err, sizeof(g_err), "batched ADMM iteration: %s", hipGetErrorString(e));
+                return bail(-1);
+            }
+        }
+    for (int q = 0; q < n; ++q) {
+        const SmallAdmmMember &M = mem[order[q]];
+        const double *mir = b->amir_h + 4L * ev0[q];
+        for (int k = 0; k < M.P->K; ++k)
+            for (int t = 0; t < 3; ++t) M.host_tot[4 * k + t] = mir[4 * k + t];
+        *M.host_cg = mir[3];
+    }
+    if (launches) *launches += nlaunch;
     return 0;
 }
 

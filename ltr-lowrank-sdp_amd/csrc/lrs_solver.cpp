@@ -243,6 +243,16 @@ struct lrs_batch {
     std::atomic<long> alone{0};   // single-workgroup inner-loop calls that launched on their own
     std::vector<long> hist;       // rounds by width, of the last call
     bool busy = false;
+    // the ADMM phase's own rendezvous (members inside admm_optimize whose iteration is wholly
+    // the one-workgroup form): independent of rdv, so a member in one phase never waits for
+    // members in the other
+    BatchRendezvous admm_rdv;
+    std::vector<SmallAdmmMember> admm_sub;
+    std::string admm_round_err;
+    bool admm_on = true;               // LRS_BATCH_ADMM, read at each lrs_solve_batch
+    int admm_launches = 0;             // combined ADMM launches (one ADMM round at a time)
+    std::atomic<long> admm_alone{0};   // ADMM iterations that members ran on their own stream
+    std::vector<long> admm_hist;
 };
 
 // ------------------------------------------------------------------------
@@ -2546,6 +2556,25 @@ static int update_dimacs_admm(lrs_ctx *c) {   // lorads_alg_common.c:454-462
     OPC(launch_avg(c->dp.NRpad, c->W.U, c->W.V, c->W.R, c->st));
     return update_dimacs(c, c->W.R, nullptr, false);
 }
+// the one-launch evaluation's host part: the cones' partials (pinned, kHpRead) in cone order
+static void admm_eval_small_sums(lrs_ctx *c, double *pinf, double *obj, double *blam) {
+    double r2 = 0.0, o = 0.0, bl = 0.0;
+    for (int k = 0; k < c->dp.K; ++k) {
+        r2 += c->hpin[kHpRead + 4 * k];
+        o += c->hpin[kHpRead + 4 * k + 1];
+        bl += c->hpin[kHpRead + 4 * k + 2];
+    }
+    *pinf = std::sqrt(r2) / (1 + c->hp.bNrm1);
+    *obj = o;
+    *blam = bl;
+}
+static void admm_eval_finish(lrs_ctx *c, double pinf, double obj, double blam) {
+    c->pObjVal = obj / c->scaleObjHis;
+    c->dObjVal = blam / c->scaleObjHis;
+    c->dimPinf = pinf;
+    const double gap = c->pObjVal - c->dObjVal;
+    c->dimGap = std::fabs(gap) / (1 + std::fabs(c->pObjVal) + std::fabs(c->dObjVal));
+}
 // LORADSCalObjUV_ADMM (lorads_admm.c:398-410) + cal_dual_obj + update_dimacs_admm (lorads_admm.c:155-157) in one pass: the
 // objective <C, R R^T> of R = (U + V) / 2 comes out of the same SDDMM as A(R R^T), so the
 // three evaluations share one set of launches and one host read
@@ -2560,24 +2589,12 @@ static int admm_eval(lrs_ctx *c) {
         OPC(launch_small_eval(c->dp, c->W, c->W.U, c->W.V, c->W.tot, c->st));
         HIPC(hipMemcpyAsync(c->hpin + kHpRead, c->W.tot, sizeof(double) * 4 * K, hipMemcpyDeviceToHost, c->st));
         HIPC(hipStreamSynchronize(c->st));
-        double r2 = 0.0;
-        obj = 0.0;
-        blam = 0.0;
-        for (int k = 0; k < K; ++k) {
-            r2 += c->hpin[kHpRead + 4 * k];
-            obj += c->hpin[kHpRead + 4 * k + 1];
-            blam += c->hpin[kHpRead + 4 * k + 2];
-        }
-        pinf = std::sqrt(r2) / (1 + c->hp.bNrm1);
+        admm_eval_small_sums(c, &pinf, &obj, &blam);
     } else {
         OPC(launch_avg(c->dp.NRpad, c->W.U, c->W.V, c->W.R, c->st));
         if (op_constr_xx(c, c->W.R, nullptr, &pinf, &obj, &blam)) return -1;
     }
-    c->pObjVal = obj / c->scaleObjHis;
-    c->dObjVal = blam / c->scaleObjHis;
-    c->dimPinf = pinf;
-    const double gap = c->pObjVal - c->dObjVal;
-    c->dimGap = std::fabs(gap) / (1 + std::fabs(c->pObjVal) + std::fabs(c->dObjVal));
+    admm_eval_finish(c, pinf, obj, blam);
     return 0;
 }
 
@@ -2592,8 +2609,36 @@ static void admm_log(lrs_ctx *c, const lrs_params *p, const AdmmState &st, doubl
 // LORADSADMMOptimize (lorads_admm.c:84-209); reopt = LORADSADMMOptimize_reopt (:222-363):
 // CG tolerance 1e-4 pinf, bad-gap budget 200, exit on l_1 pinf only with the gap met,
 // rho schedule on iter instead of iter + 1.
+// Whether this context's ADMM iteration is wholly the one-workgroup form: admm_update_var takes
+// one k_small_cg launch a side and admm_eval the k_small_eval launch (what a round combines).
+static bool admm_round_form(lrs_ctx *c) {
+    const char *eb = getenv("LRS_SMALL_CG_BATCH"), *ev = getenv("LRS_SMALL_EVAL");
+    if ((eb && eb[0] == '0') || (ev && ev[0] == '0')) return false;
+    if (!use_small_cg(c, 0)) return false;   // LRS_SMALL_CG, an LP block, a dense-A cone
+    if (c->dp.K > 1 && !small_cg_batch_fits(c->dp)) return false;
+    return small_eval_fits(c->dp) && small_admm_fits(c->dp);
+}
+// One ADMM iteration of a member of the batch's ADMM quorum, in place of admm_update_var +
+// admm_eval: no launch of its own; its arguments go to the round that the last member to park
+// launches for all.  The stream's earlier work (the previous iteration's dual update, the oracle
+// rank's launches) completes first: the round's streams take no event of this one.
+static int admm_round_iteration(lrs_ctx *c, double rho, double tol, int maxit) {
+    lrs_batch *b = c->batch;
+    HIPC(hipStreamSynchronize(c->st));
+    b->admm_sub[c->batch_idx] = SmallAdmmMember{&c->dp, &c->W, rho, tol, maxit, c->hpin + kHpRead, c->hpin + kHpCgTotal};
+    if (b->admm_rdv.submit(c->batch_idx)) { set_err("batched ADMM iteration: %s", b->admm_round_err.c_str()); return -1; }
+    c->cg_dev_total = true;
+    double pinf, obj, blam;
+    admm_eval_small_sums(c, &pinf, &obj, &blam);
+    admm_eval_finish(c, pinf, obj, blam);
+    return 0;
+}
 static int admm_optimize(lrs_ctx *c, lrs_params *p, AdmmState &st, long ceiling, double tss, bool reopt = false) {
     if (st.gap <= p->phase2Tol && st.pinf1 <= p->phase2Tol) return 0;
+    // a member of a batched solve is in the ADMM quorum from here to every exit, error returns
+    // included, if its iteration is the one-workgroup form (LRS_BATCH_ADMM=0: never)
+    const bool round = c->batch && c->batch->admm_on && admm_round_form(c);
+    BatchRendezvous::Scope quorum(c->batch ? &c->batch->admm_rdv : nullptr, c->batch_idx, round);
     const int maxCG = 800;
     const double orig = now_s();
     st.rho = std::min(st.rho, p->rhoMax);
@@ -2611,8 +2656,13 @@ static int admm_optimize(lrs_ctx *c, lrs_params *p, AdmmState &st, long ceiling,
             break;
         }
         const double cgtol = std::min(st.pinf1 * (reopt ? 1e-4 : 1e-2), 1e-8);
-        if (admm_update_var(c, st.rho, cgtol, maxCG)) return -1;
-        if (admm_eval(c)) return -1;
+        if (round) {
+            if (admm_round_iteration(c, st.rho, cgtol, maxCG)) return -1;
+        } else {
+            if (c->batch) c->batch->admm_alone++;
+            if (admm_update_var(c, st.rho, cgtol, maxCG)) return -1;
+            if (admm_eval(c)) return -1;
+        }
         st.cg_iter = c->cgIterTotal + (c->cg_dev_total ? (long)c->hpin[kHpCgTotal] : 0);
         st.pobj = c->pObjVal; st.dobj = c->dObjVal; st.pinf1 = c->dimPinf;
         st.pinfinf = st.pinf1 * (1 + c->hp.bNrm1) / (1 + c->hp.bNrmInf);
@@ -3299,6 +3349,15 @@ int lrs_op_admm_constr(lrs_ctx *c) {
     return 0;
 }
 
+// the half-step's right-hand side of `cone` (W.cg_b) as a column-major n x r matrix
+static int read_cg_rhs(lrs_ctx *c, int cone, double *rhs) {
+    const DevCone &d = c->dp.cones[cone];
+    std::vector<double> h((size_t)d.n * d.ld);
+    HIPC(hipMemcpy(h.data(), c->W.cg_b + d.foff, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    for (int q = 0; q < d.r; ++q)
+        for (int i = 0; i < d.n; ++i) rhs[i + (long)q * d.n] = h[(long)i * d.ld + q];
+    return 0;
+}
 int lrs_op_admm_half(lrs_ctx *c, int cone, int side, double rho, double cg_tol, int cg_maxit, int *cg_iters,
                      double *rhs) {
     LRS_NEED_STATE(c);
@@ -3326,13 +3385,7 @@ int lrs_op_admm_half(lrs_ctx *c, int cone, int side, double rho, double cg_tol, 
         if (dev) HIPC(hipMemcpy(&it, c->W.cgc + CG_ITERS, sizeof(double), hipMemcpyDeviceToHost));
         *cg_iters = (int)it;
     }
-    if (rhs) {
-        const DevCone &d = P.cones[cone];
-        std::vector<double> h((size_t)d.n * d.ld);
-        HIPC(hipMemcpy(h.data(), c->W.cg_b + d.foff, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-        for (int q = 0; q < d.r; ++q)
-            for (int i = 0; i < d.n; ++i) rhs[i + (long)q * d.n] = h[(long)i * d.ld + q];
-    }
+    if (rhs) return read_cg_rhs(c, cone, rhs);
     return 0;
 }
 
@@ -3696,6 +3749,24 @@ int lrs_solve_batch(lrs_batch *b, lrs_ctx **ctxs, int n, const lrs_params *param
         if (r) b->round_err = last_device_error();
         return r;
     });
+    // the ADMM phase's rendezvous: nobody is in its quorum until a member's admm_optimize joins
+    {
+        const char *ea = getenv("LRS_BATCH_ADMM");
+        b->admm_on = !(ea && ea[0] == '0');
+    }
+    b->admm_sub.assign(n, SmallAdmmMember{});
+    b->admm_round_err.clear();
+    b->admm_launches = 0;
+    b->admm_alone = 0;
+    small_admm_batch_reset(b->sb);
+    b->admm_rdv.reset(n, [b](const std::vector<int> &mem) -> int {
+        std::vector<SmallAdmmMember> m;
+        m.reserve(mem.size());
+        for (int i : mem) m.push_back(b->admm_sub[i]);
+        const int r = launch_small_admm_batch(b->sb, m.data(), (int)m.size(), &b->admm_launches);
+        if (r) b->admm_round_err = last_device_error();
+        return r;
+    });
     // every member counts towards the quorum until its solve decides otherwise (its ALM phase takes
     // another inner loop, or it fails before that phase), so the first round waits for all of them
     for (int i = 0; i < n; ++i) b->rdv.enter(i);
@@ -3711,12 +3782,14 @@ int lrs_solve_batch(lrs_batch *b, lrs_ctx **ctxs, int n, const lrs_params *param
             c->batch_idx = i;
             rc[i] = solve_impl(c, &prm, &res[i]);
             b->rdv.leave(i);
+            b->admm_rdv.leave(i);
             c->batch = nullptr;
             c->batch_idx = -1;
             if (rc[i]) b->errs[i] = g_lrs_err;
         });
     for (auto &t : th) t.join();
     b->hist = b->rdv.width_histogram();
+    b->admm_hist = b->admm_rdv.width_histogram();
     b->busy = false;
     bind(ctxs[0]);
     int bad = 0, first = -1;
@@ -3740,17 +3813,85 @@ int lrs_batch_stats(lrs_batch *b, long *launches, int *widest, long *served, lon
     if (alone) *alone = b->alone.load();
     return 0;
 }
-int lrs_batch_round_widths(lrs_batch *b, long *out, int cap, long *rounds) {
-    LRS_NEED_ARG(b);
+static void batch_widths(const std::vector<long> &hist, long *out, int cap, long *rounds) {
     long tot = 0;
-    for (int w = 0; w < (int)b->hist.size(); ++w) {
-        if (out && w < cap) out[w] = b->hist[w];
-        tot += b->hist[w];
+    for (int w = 0; w < (int)hist.size(); ++w) {
+        if (out && w < cap) out[w] = hist[w];
+        tot += hist[w];
     }
     if (out)
-        for (int w = (int)b->hist.size(); w < cap; ++w) out[w] = 0;
+        for (int w = (int)hist.size(); w < cap; ++w) out[w] = 0;
     if (rounds) *rounds = tot;
+}
+int lrs_batch_round_widths(lrs_batch *b, long *out, int cap, long *rounds) {
+    LRS_NEED_ARG(b);
+    batch_widths(b->hist, out, cap, rounds);
     return 0;
+}
+int lrs_batch_admm_stats(lrs_batch *b, long *launches, int *widest, long *served, long *alone) {
+    LRS_NEED_ARG(b);
+    long rounds = 0;
+    b->admm_rdv.stats(&rounds, widest, served);
+    if (launches) *launches = b->admm_launches;
+    if (alone) *alone = b->admm_alone.load();
+    return 0;
+}
+int lrs_batch_admm_round_widths(lrs_batch *b, long *out, int cap, long *rounds) {
+    LRS_NEED_ARG(b);
+    batch_widths(b->admm_hist, out, cap, rounds);
+    return 0;
+}
+int lrs_batch_admm_shape(lrs_batch *b, int *variants, int *blocks) {
+    LRS_NEED_ARG(b);
+    if (variants) *variants = 0;
+    if (blocks) *blocks = 0;
+    if (b->sb) small_admm_batch_shape(b->sb, variants, blocks);
+    return 0;
+}
+// Operator-level access to the round (tests): one ADMM iteration's launches -- both sides'
+// half-steps of every cone, then the evaluation -- for the given contexts through
+// launch_small_admm_batch, from the state lrs_op_admm_constr leaves, as lrs_op_admm_half steps
+// one cone's launch.  No dual update.
+int lrs_op_admm_round(lrs_batch *b, lrs_ctx **ctxs, int n, const double *rho, const double *cg_tol, int cg_maxit) {
+    LRS_NEED_ARG(b);
+    LRS_NEED_ARG(ctxs);
+    LRS_NEED_ARG(rho);
+    LRS_NEED_ARG(cg_tol);
+    if (n < 1 || n > LRS_BATCH_MAX) { set_err("lrs_op_admm_round: %d instances (1 to %d)", n, LRS_BATCH_MAX); return -1; }
+    if (b->busy) { set_err("lrs_op_admm_round: the batch object is in use"); return -1; }
+    std::vector<SmallAdmmMember> m;
+    for (int i = 0; i < n; ++i) {
+        lrs_ctx *c = ctxs[i];
+        LRS_NEED_STATE(c);
+        if (c->device != ctxs[0]->device || (b->sb && b->device != c->device)) { set_err("lrs_op_admm_round: instance %d: another device", i); return -1; }
+        if (sharded(c) || !admm_round_form(c)) { set_err("lrs_op_admm_round: instance %d: its ADMM iteration is not the one-workgroup form", i); return -1; }
+        if (!(rho[i] > 0.0) || cg_maxit < 1) { set_err("lrs_op_admm_round: rho %g, cg_maxit %d", rho[i], cg_maxit); return -1; }
+        HIPC(hipStreamSynchronize(c->st));
+        m.push_back(SmallAdmmMember{&c->dp, &c->W, rho[i], cg_tol[i], cg_maxit, c->hpin + kHpRead, c->hpin + kHpCgTotal});
+    }
+    bind(ctxs[0]);
+    if (!b->sb) {
+        OPC(small_batch_create(&b->sb, LRS_BATCH_MAX));
+        b->device = ctxs[0]->device;
+    }
+    int launches = 0;
+    OPC(launch_small_admm_batch(b->sb, m.data(), n, &launches));
+    return 0;
+}
+int lrs_admm_form(lrs_ctx *c, int *small_cg_cones, int *round_form) {
+    LRS_NEED_STATE(c);
+    int ncg = 0;
+    for (int k = 0; k < c->dp.K; ++k) ncg += use_small_cg(c, k) ? 1 : 0;
+    if (small_cg_cones) *small_cg_cones = ncg;
+    if (round_form) *round_form = (!sharded(c) && admm_round_form(c)) ? 1 : 0;
+    return 0;
+}
+// the right-hand side that the last half-step of `cone` left (column-major n x r, as lrs_op_admm_half's)
+int lrs_op_admm_rhs(lrs_ctx *c, int cone, double *rhs) {
+    LRS_NEED_STATE(c);
+    LRS_NEED_ARG(rhs);
+    if (cone < 0 || cone >= c->dp.K) { set_err("lrs_op_admm_rhs: cone %d of %d", cone, c->dp.K); return -1; }
+    return read_cg_rhs(c, cone, rhs);
 }
 
 int lrs_trajectory(lrs_ctx *c, int phase, int *curr, int *orc, int cap) {

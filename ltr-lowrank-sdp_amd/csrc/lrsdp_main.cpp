@@ -250,6 +250,9 @@ static int run_batch(const Flags &base, const char *prog) {
         lrs_batch_stats(b, &launches, &widest, &served, &alone);
         printf("batch: %zu instances, %ld combined launches (widest round %d), %ld inner-loop calls served, %ld alone\n",
                live.size(), launches, widest, served, alone);
+        lrs_batch_admm_stats(b, &launches, &widest, &served, &alone);
+        printf("batch ADMM: %ld combined launches (widest round %d members), %ld iterations served, %ld alone\n",
+               launches, widest, served, alone);
         lrs_batch_destroy(b);
     }
     for (Job *j : jobs) {

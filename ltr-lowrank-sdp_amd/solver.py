@@ -159,6 +159,12 @@ def load_library(path=None):
         "lrs_batch_error": (C.c_char_p, [vp, C.c_int]),
         "lrs_batch_stats": (C.c_int, [vp, C.POINTER(C.c_long), ip, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
         "lrs_batch_round_widths": (C.c_int, [vp, C.POINTER(C.c_long), C.c_int, C.POINTER(C.c_long)]),
+        "lrs_batch_admm_stats": (C.c_int, [vp, C.POINTER(C.c_long), ip, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+        "lrs_batch_admm_round_widths": (C.c_int, [vp, C.POINTER(C.c_long), C.c_int, C.POINTER(C.c_long)]),
+        "lrs_batch_admm_shape": (C.c_int, [vp, ip, ip]),
+        "lrs_op_admm_round": (C.c_int, [vp, C.POINTER(vp), C.c_int, dp, dp, C.c_int]),
+        "lrs_op_admm_rhs": (C.c_int, [vp, C.c_int, dp]),
+        "lrs_admm_form": (C.c_int, [vp, ip, ip]),
         "lrs_shard_plan": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_long), ip, ip, ip, ip, ip, ip, ip]),
     }
     for name, (res, args) in sig.items():
@@ -412,6 +418,19 @@ class Solver:
         self._check(self.lib.lrs_op_admm_half(self.ctx, cone, side, rho, cg_tol, cg_maxit, C.byref(it), _dptr(rhs)),
                     "admm_half")
         return self.get_factor(V if side else U), rhs, it.value
+
+    def admm_form(self):
+        """(cones whose ADMM half-step is the single-workgroup kernel, whether the whole iteration
+        is the one-workgroup form a batch's ADMM meeting combines), at the current ranks."""
+        ncg, form = C.c_int(), C.c_int()
+        self._check(self.lib.lrs_admm_form(self.ctx, C.byref(ncg), C.byref(form)), "admm_form")
+        return ncg.value, bool(form.value)
+
+    def admm_rhs(self, cone=0):
+        """The right-hand side that the last half-step of `cone` left (as admm_half's)."""
+        rhs = np.empty(self.dims[cone] * self.get_rank()[cone])
+        self._check(self.lib.lrs_op_admm_rhs(self.ctx, cone, _dptr(rhs)), "admm_rhs")
+        return rhs
 
     def dual_update(self, rho):
         """LORADSUpdateDualVar: lambda += rho (b - A(X))."""
@@ -828,6 +847,36 @@ class Batch:
         """{width: rounds} of the last solve."""
         h = (C.c_long * (BATCH_MAX + 1))()
         if self.lib.lrs_batch_round_widths(self.h, h, BATCH_MAX + 1, None) != 0:
+            raise RuntimeError(self.lib.lrs_last_error().decode())
+        return {w: h[w] for w in range(BATCH_MAX + 1) if h[w]}
+
+    def admm_stats(self):
+        """The ADMM meeting's counters of the last solve: combined launches, the widest round in
+        members, iterations served by rounds, iterations members ran alone; plus the most kernel
+        variants in one round and the most blocks in one half-step launch."""
+        la, se, al = C.c_long(), C.c_long(), C.c_long()
+        wi, va, bl = C.c_int(), C.c_int(), C.c_int()
+        if self.lib.lrs_batch_admm_stats(self.h, C.byref(la), C.byref(wi), C.byref(se), C.byref(al)) != 0:
+            raise RuntimeError(self.lib.lrs_last_error().decode())
+        if self.lib.lrs_batch_admm_shape(self.h, C.byref(va), C.byref(bl)) != 0:
+            raise RuntimeError(self.lib.lrs_last_error().decode())
+        return {"launches": la.value, "widest": wi.value, "served": se.value, "alone": al.value,
+                "variants": va.value, "blocks": bl.value}
+
+    def admm_round(self, solvers, rho, cg_tol, cg_maxit=800):
+        """One ADMM iteration's shared launches for `solvers` (each after admm_constr): both sides'
+        half-steps of every cone, then the evaluation (lrs_op_admm_round).  rho, cg_tol: one a solver."""
+        n = len(solvers)
+        ctxs = (C.c_void_p * n)(*[sv.ctx for sv in solvers])
+        r = (C.c_double * n)(*[float(x) for x in rho])
+        t = (C.c_double * n)(*[float(x) for x in cg_tol])
+        if self.lib.lrs_op_admm_round(self.h, ctxs, n, r, t, cg_maxit) != 0:
+            raise RuntimeError(f"admm_round: {self.lib.lrs_last_error().decode()}")
+
+    def admm_round_widths(self):
+        """{members: rounds} of the last solve's ADMM meeting."""
+        h = (C.c_long * (BATCH_MAX + 1))()
+        if self.lib.lrs_batch_admm_round_widths(self.h, h, BATCH_MAX + 1, None) != 0:
             raise RuntimeError(self.lib.lrs_last_error().decode())
         return {w: h[w] for w in range(BATCH_MAX + 1) if h[w]}
 

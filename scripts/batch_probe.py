@@ -11,7 +11,12 @@ solves.  The contexts are created and every way is run once before the timing; e
 is a host clock around calls that end in a stream synchronise.  `--repeats` interleaved repeats
 (a, b, c, a, b, c, ...); median and range of each, the batch's counters and its rounds by width.
 
-    python scripts/batch_probe.py [--B 32] [--repeats 5] [--json out.json] [--md out.md]
+`--legs whole` (or `phase1`) keeps one leg; `--flag disableOracle=1` (repeatable) adds a solver
+parameter to every leg, e.g. to take the rank oracle's Gram out of the ADMM iterations.  Where the
+library has the ADMM meeting, its counters (lrs_batch_admm_stats) and rounds by width are reported
+beside the ALM meeting's; the script also runs on a build without them, for an A/B.
+
+    python scripts/batch_probe.py [--B 32] [--repeats 5] [--legs both] [--flag k=v] [--json out.json] [--md out.md]
 """
 import argparse
 import ctypes as C
@@ -101,6 +106,9 @@ def run_set(name, problems, kw, repeats):
     out = {"set": name, "B": B, "flags": kw, "alm_inner_total": sum(inner["c batch"]),
            "alm_inner_max": max(inner["c batch"]), "batch_stats": batch.stats(),
            "round_widths": batch.round_widths(),
+           "admm_stats": batch.admm_stats() if hasattr(batch, "admm_stats") else None,
+           "admm_round_widths": batch.admm_round_widths() if hasattr(batch, "admm_round_widths") else None,
+           "admm_iter_total": sum(int(res[i].admm_iter) for i in range(B)),
            "seconds": {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "all": v}
                        for k, v in times.items()}}
     for sv in svs:
@@ -115,6 +123,8 @@ def to_markdown(results):
         s = r["seconds"]
         cell = lambda k: f"{s[k]['median'] * 1e3:.2f} ({s[k]['min'] * 1e3:.2f} .. {s[k]['max'] * 1e3:.2f})"
         leg = "phase 1 (skipADMM=1)" if r["flags"].get("skipADMM") else "whole solve"
+        extra = {k: v for k, v in r["flags"].items() if k != "skipADMM"}
+        leg += f" {extra}" if extra else ""
         lines.append(f"| {r['set']} (B = {r['B']}) | {leg} | {cell('a sequential')} | {cell('b threads')} | "
                      f"{cell('c batch')} | {s['a sequential']['median'] / s['c batch']['median']:.2f} | "
                      f"{s['b threads']['median'] / s['c batch']['median']:.2f} |")
@@ -123,6 +133,9 @@ def to_markdown(results):
         leg = "phase 1" if r["flags"].get("skipADMM") else "whole solve"
         lines.append(f"* {r['set']}, {leg}: inner iterations {r['alm_inner_total']} in all, longest member "
                      f"{r['alm_inner_max']}; lrs_batch_stats {r['batch_stats']}; rounds by width {r['round_widths']}")
+        if r.get("admm_stats") is not None:
+            lines.append(f"  * ADMM iterations {r['admm_iter_total']} in all; lrs_batch_admm_stats {r['admm_stats']}; "
+                         f"ADMM rounds by width {r['admm_round_widths']}")
     return "\n".join(lines)
 
 
@@ -130,12 +143,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--legs", choices=("both", "phase1", "whole"), default="both")
+    ap.add_argument("--flag", action="append", default=[], help="k=v: a solver parameter for every leg")
     ap.add_argument("--json")
     ap.add_argument("--md")
     a = ap.parse_args()
     results = []
     for name, problems in make_sets(a.B).items():
         for kw in ({"skipADMM": 1}, {}):
+            if a.legs != "both" and (a.legs == "phase1") != bool(kw):
+                continue
+            for f in a.flag:
+                k, v = f.split("=", 1)
+                kw[k] = float(v) if "." in v or "e" in v.lower() else int(v)
             results.append(run_set(name, problems, kw, a.repeats))
             print(json.dumps(results[-1]), flush=True)
     md = to_markdown(results)
