@@ -251,6 +251,43 @@ int lrs_op_admm_rhs(lrs_ctx *ctx, int cone, double *rhs);
  * half-step is the single-workgroup kernel, and whether the whole iteration is the
  * one-workgroup form that the ADMM meeting of a batch combines. */
 int lrs_admm_form(lrs_ctx *ctx, int *small_cg_cones, int *round_form);
+/* ---- Sign rounding of a factor for diagonally constrained cones.  No reference
+ * counterpart (the reference stops at the factor).  For a cone whose constraints are X_ii = b_i for
+ * every i and nothing else (MaxCut's relaxation: n consecutive constraints, constraint o + i the
+ * single entry (i, i), none of them touching another cone), every b_i > 0, the objective in the
+ * slot pattern, and a factor X (n x r, `which` one of LRS_R .. LRS_V) it draws `trials` hyperplanes
+ * g_t in R^r (a multiple of 64, 64 .. 4096), sets s_i^t = +1 if <X_i, g_t> >= 0 else -1, x_i^t =
+ * sqrt(b_i) s_i^t, and evaluates value_t = <C, x^t x^t^T> = sum_i C_ii b_i + 2 sum_{j<i} C_ij
+ * sqrt(b_i b_j) s_i^t s_j^t in the units of the instance file (C = -F0: the units of
+ * lrs_result.pobj and the JSON's primal_obj, whatever a reopt round scaled on the device): the
+ * objective of a feasible rank-one point, an upper bound on the optimum over such points next to
+ * the relaxation's lower bound pobj.  All of it on the device and the context's stream: a
+ * projection kernel, a value kernel with a fixed-order finish (no float atomics: bitwise
+ * reproducible) and, with local_search != 0, a one-flip descent per trial in between: rows
+ * i = 0 .. n - 1 swept in order (Gauss-Seidel), f = sum_{j != i} C_ij sqrt(b_i b_j) s_j in
+ * adjacency (column) order, s_i flipped iff that lowers the value (-4 s_i f < 0, strictly), sweeps
+ * repeated until one flips nothing in that trial or max_sweeps (<= 0: 50) have run.
+ * dirs: r x trials column-major (trial t's direction at dirs + r t), or NULL: lrs_round_dirs(seed,
+ * r, trials, .) is generated on the host and uploaded (no device generator).  Outputs, each may be
+ * NULL: values[trials]; bits[trials / 64][n], bit t of bits[w][i] set iff s_i^(64 w + t) = +1;
+ * best_trial, the smallest value's trial, the lowest index on ties; best_value; best_x[n] that
+ * trial's signs (+1 / -1); sweeps, the sweeps the descent ran (the most over the trials; the last
+ * one, which flips nothing, counts; 0 without local_search).
+ * Refusals, each a negative code with its message in lrs_last_error() and nothing started: -2
+ * trials not a multiple of 64 or out of range, -3 a sharded context, -4 no such cone, -5 the LP
+ * block, -6 ranks not set, -7 a cone that is not diagonally constrained in the sense above, -8 a
+ * b_i <= 0, -9 a dense or constant objective, -10 dense or rank-one constraint matrices, -11 a
+ * selector other than LRS_R .. LRS_V (-1: the header's general failures).
+ * lrs_round_dirs (host only, no context): the seeded directions, out[c + r t] for column c of
+ * trial t: with mix(x) = splitmix64's output function of x + 0x9E3779B97F4A7C15 (z = that sum; z =
+ * (z ^ z >> 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) 0x94D049BB133111EB; z ^ z >> 31; mod 2^64),
+ * h = mix(mix(seed) ^ (t 2^32 + c)), a = mix(h), b = mix(a), u1 = ((a >> 11) + 1) 2^-53, u2 =
+ * (b >> 11) 2^-53, and the entry is sqrt(-2 ln u1) cos(6.283185307179586 u2) (Box-Muller).  A
+ * seeded lrs_round_signs equals the call with these directions passed explicitly. */
+int lrs_round_dirs(unsigned long long seed, int r, int trials, double *out);
+int lrs_round_signs(lrs_ctx *ctx, int cone, int which, int trials, const double *dirs, unsigned long long seed,
+                    int local_search, int max_sweeps, double *values, unsigned long long *bits, int *best_trial,
+                    double *best_value, signed char *best_x, int *sweeps);
 /* trajectory (phase 1 then phase 2) after lrs_solve: curr and oracle ranks */
 int lrs_trajectory(lrs_ctx *ctx, int phase, int *curr_rank, int *oracle_rank, int cap);
 /* JSON like lorads_logging.c:618-712 */

@@ -505,6 +505,23 @@ long lp_sweep_scratch(const DevProblem &P);
 int launch_small_cg_batch(const DevProblem &P, DevWork &W, int side, double rho, double tol, int maxit,
                           hipStream_t st);
 
+// ---- sign rounding of a factor (lrs_kernels.hip "Sign rounding") ----
+// T trials (a multiple of 64) of one cone, their signs as bit words bits[T / 64][n] (bit t of
+// word w: trial 64 w + t, set = +1).  launch_round_prep: wadj[e] = Craw[slot_e] sb[i] sb[j] per
+// adjacency entry (Craw the unscaled slot values, sb[n] = sqrt(b_i)).  launch_round_proj: the
+// signs of X dirT (X the cone's rows, n x ld; dirT r x T row-major).  launch_round_value:
+// values[t] = <C, x_t x_t^T> through part (T round_chunks(n) doubles), summed in chunk order.
+// launch_round_descent: Gauss-Seidel one-flip descent on the words in place, at most max_sweeps
+// sweeps; sweeps[T / 64] = the sweeps each word's wave ran.
+int round_chunks(int n);
+int launch_round_prep(const DevCone &c, const double *Craw, const double *sb, double *wadj, hipStream_t st);
+int launch_round_proj(const DevCone &c, const double *X, int T, const double *dirT, unsigned long long *bits,
+                      hipStream_t st);
+int launch_round_value(const DevCone &c, int T, const double *wadj, const unsigned long long *bits, double *part,
+                       double *values, hipStream_t st);
+int launch_round_descent(const DevCone &c, int T, const double *wadj, unsigned long long *bits, int max_sweeps,
+                         int *sweeps, hipStream_t st);
+
 // ---- dual infeasibility (Lanczos for lambda_min of S per cone) ----
 // y = S x over one cone's adjacency (S on the global slots, x / y cone-local vectors)
 int launch_symv(const DevProblem &P, int cone, const double *S, const double *x, double *y, hipStream_t st);

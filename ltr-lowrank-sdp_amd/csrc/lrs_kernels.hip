@@ -9602,4 +9602,237 @@ int launch_lp_admm(const DevProblem &P, DevWork &W, double rho, hipStream_t st) 
     return 0;
 }
 
+// ------------------------------------------------------------------------
+// Sign rounding of a factor (no reference counterpart).  lane = trial: the T
+// trial signs of row i are T / 64 bit words, bits[w][i] holding trials 64 w .. 64 w + 63 (bit set
+// = +1), so one wave carries 64 trials through every kernel and a sign product is one xor.
+// ------------------------------------------------------------------------
+constexpr int kRoundRows = 32;    // factor rows of one projection block (8 a wave)
+constexpr int kRoundWords = 4;    // sign words (256 trials) of one projection block
+constexpr int kRoundCols = 16;    // factor columns whose directions are staged in LDS at a time
+constexpr int kRoundChunk = 32;   // fewest rows of one value-kernel wave
+constexpr int kRoundMaxChunks = 1024;
+
+__device__ __forceinline__ unsigned long long read_lane_u64(unsigned long long b, int l) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)b, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), l);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// wadj[e] = C_ij sqrt(b_i b_j) per adjacency entry of the cone (the diagonal: C_ii b_i), C in the
+// instance file's units (the caller passes the unscaled slot values), sb[i] = sqrt(b_i)
+__global__ void __launch_bounds__(kBlock) k_round_prep(int n, const int *__restrict__ adj_ptr,
+                                                       const int *__restrict__ adj_col,
+                                                       const int *__restrict__ adj_slot,
+                                                       const double *__restrict__ Craw,
+                                                       const double *__restrict__ sb, double *__restrict__ wadj) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const double si = sb[i];
+    for (int e = adj_ptr[i]; e < adj_ptr[i + 1]; ++e) wadj[e] = Craw[adj_slot[e]] * (si * sb[adj_col[e]]);
+}
+
+// Projection: bits[w][i] = ballot_t(<X_i, g_t> >= 0).  A block takes kRoundRows rows and
+// kRoundWords words; the directions (dirT: r x T row-major) pass through LDS kRoundCols columns
+// at a time, so any r up to kMaxRankLd fits in 32 KiB.  A wave holds 8 rows: the rows' columns
+// of the chunk sit one a lane (16 lanes a row) and reach the FMA as wave-uniform operands, lane
+// t accumulates trial t's dot in column order.  Only columns c < r are read: the padding
+// r .. ld - 1 contributes nothing.
+__global__ void __launch_bounds__(kBlock) k_round_proj(int n, int r, int ld, int T, const double *__restrict__ X,
+                                                       const double *__restrict__ dirT,
+                                                       unsigned long long *__restrict__ bits) {
+    __shared__ double sd[kRoundCols][kRoundWords * 64];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int w0 = blockIdx.y * kRoundWords;
+    const int nw = min(kRoundWords, T / 64 - w0);
+    const int i0 = blockIdx.x * kRoundRows + wv * 8;
+    double acc[8][kRoundWords];
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int w = 0; w < kRoundWords; ++w) acc[q][w] = 0.0;
+    for (int c0 = 0; c0 < r; c0 += kRoundCols) {
+        const int nc = min(kRoundCols, r - c0);
+        __syncthreads();
+        for (int q = threadIdx.x; q < kRoundCols * kRoundWords * 64; q += kBlock) {
+            const int c = q / (kRoundWords * 64), t = q % (kRoundWords * 64);
+            sd[c][t] = (c < nc && t < nw * 64) ? dirT[(long)(c0 + c) * T + (long)w0 * 64 + t] : 0.0;
+        }
+        __syncthreads();
+        double xv[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = i0 + h * 4 + (lane >> 4), c = c0 + (lane & 15);
+            xv[h] = (i < n && c < r) ? X[(long)i * ld + c] : 0.0;
+        }
+        for (int c = 0; c < nc; ++c) {
+            double g[kRoundWords];
+#pragma unroll
+            for (int w = 0; w < kRoundWords; ++w) g[w] = sd[c][w * 64 + lane];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const double x = read_lane(xv[q >> 2], (q & 3) * 16 + c);
+#pragma unroll
+                for (int w = 0; w < kRoundWords; ++w) acc[q][w] += x * g[w];
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int i = i0 + q;
+        if (i >= n) break;
+#pragma unroll
+        for (int w = 0; w < kRoundWords; ++w) {
+            if (w >= nw) break;
+            const unsigned long long b = __ballot(acc[q][w] >= 0.0);
+            if (lane == 0) bits[(long)(w0 + w) * n + i] = b;
+        }
+    }
+}
+
+// Values: wave (chunk ch, word w) walks the lower adjacency of its rows; every load has one
+// address for all lanes, lane t keeps trial 64 w + t's sum of C_ii b_i + 2 sum_{j<i} C_ij
+// sqrt(b_i b_j) s_i s_j over the chunk's rows.  part[(w nch + ch) 64 + lane].
+__global__ void __launch_bounds__(kBlock) k_round_value(int n, int rows, int nch, const int *__restrict__ adj_ptr,
+                                                        const int *__restrict__ adj_low,
+                                                        const int *__restrict__ adj_col,
+                                                        const double *__restrict__ wadj,
+                                                        const unsigned long long *__restrict__ bits,
+                                                        double *__restrict__ part) {
+    const int lane = threadIdx.x & 63;
+    const int ch = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (ch >= nch) return;
+    const int w = blockIdx.y;
+    const unsigned long long *__restrict__ bw = bits + (long)w * n;
+    const int i1 = min(n, (ch + 1) * rows);
+    double acc = 0.0;
+    for (int i = ch * rows; i < i1; ++i) {
+        const unsigned long long bi = bw[i];
+        const int e1 = adj_low[i];
+        for (int e = adj_ptr[i]; e < e1; ++e) {
+            const int j = adj_col[e];
+            const double c = wadj[e];
+            const double cw = j == i ? c : 2.0 * c;
+            acc += (((bi ^ bw[j]) >> lane) & 1ull) ? -cw : cw;
+        }
+    }
+    part[((long)w * nch + ch) * 64 + lane] = acc;
+}
+// values[t] = the chunks' partials in chunk order (no atomics: the same bits every run)
+__global__ void __launch_bounds__(kBlock) k_round_fin(int T, int nch, const double *__restrict__ part,
+                                                      double *__restrict__ values) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= T) return;
+    const double *p = part + (long)(t >> 6) * nch * 64 + (t & 63);
+    double s = 0.0;
+    for (int ch = 0; ch < nch; ++ch) s += p[(long)ch * 64];
+    values[t] = s;
+}
+
+// One-flip descent: one wave a word, the 64 trials in its lanes, rows swept in order
+// (Gauss-Seidel).  f = sum_{j != i} C_ij sqrt(b_i b_j) s_j in adjacency order; the flip changes
+// the value by -4 s_i f and is taken iff that is < 0; the ballot of the decisions is row i's new
+// word.  Hand-off of a stored word to the later rows that read it as a neighbour's: EVERY lane
+// stores the (identical) word, and every later load of it -- the own-word load and the
+// neighbour gather alike -- is a vector load by a lane that stored that address itself, so it is
+// ordered by the lane's own program order; no other wave touches the word's column.  The row's
+// entries are fetched one a lane (64 at a time) and reach the sum as wave-uniform operands; the
+// next row's entries and the row after's end, which do not depend on any sign, are requested a
+// row ahead, so a row waits for one memory round trip, its neighbours' words.  sweeps[w] =
+// sweeps run, the last one without a flip unless max_sweeps hit.
+__global__ void __launch_bounds__(64) k_round_descent(int n, int nnz, const int *__restrict__ adj_ptr,
+                                                      const int *__restrict__ adj_col,
+                                                      const double *__restrict__ wadj, unsigned long long *bits,
+                                                      int max_sweeps, int *__restrict__ sweeps) {
+    const int lane = threadIdx.x;
+    unsigned long long *bw = bits + (long)blockIdx.x * n;
+    // lane l's entry of a row starting at e: e + l, clamped into the cone's entries so that the
+    // load needs no branch (lanes past the row's end fetch an entry that is never used)
+    auto at = [&](int e) { return min(e + lane, nnz - 1); };
+    int s = 0;
+    while (s < max_sweeps) {
+        unsigned long long any = 0;
+        int e0 = adj_ptr[0], e1 = adj_ptr[1], e2 = adj_ptr[min(2, n)];
+        int jc = adj_col[at(e0)];
+        double cc = wadj[at(e0)];
+        for (int i = 0; i < n; ++i) {
+            // requested now, used by the next rows: the end of row i + 2, the entries of row i + 1
+            const int e3 = adj_ptr[min(i + 3, n)];
+            const int jn = adj_col[at(e1)];
+            const double cn = wadj[at(e1)];
+            const unsigned long long bi = bw[i];
+            unsigned long long bj = bw[jc];
+            double c = jc == i ? 0.0 : cc;
+            double f = 0.0;
+            int cnt = min(64, e1 - e0);
+            for (int q = 0; q < cnt; ++q) {
+                const double cq = read_lane(c, q);
+                const unsigned long long bq = read_lane_u64(bj, q);
+                f += ((bq >> lane) & 1ull) ? cq : -cq;
+            }
+            for (int eb = e0 + 64; eb < e1; eb += 64) {   // rows of more than 64 entries
+                cnt = min(64, e1 - eb);
+                const int j = adj_col[at(eb)];
+                c = j == i ? 0.0 : wadj[at(eb)];
+                bj = bw[j];
+                for (int q = 0; q < cnt; ++q) {
+                    const double cq = read_lane(c, q);
+                    const unsigned long long bq = read_lane_u64(bj, q);
+                    f += ((bq >> lane) & 1ull) ? cq : -cq;
+                }
+            }
+            const bool plus = (bi >> lane) & 1ull;
+            const unsigned long long fm = __ballot(plus ? f > 0.0 : f < 0.0);
+            if (fm) {
+                bw[i] = bi ^ fm;
+                any |= fm;
+            }
+            e0 = e1;
+            e1 = e2;
+            e2 = e3;
+            jc = jn;
+            cc = cn;
+        }
+        ++s;
+        if (!any) break;
+    }
+    if (lane == 0) sweeps[blockIdx.x] = s;
+}
+
+int round_chunk_rows(int n) { return std::max(kRoundChunk, (n + kRoundMaxChunks - 1) / kRoundMaxChunks); }
+int round_chunks(int n) { return (n + round_chunk_rows(n) - 1) / round_chunk_rows(n); }
+
+int launch_round_prep(const DevCone &c, const double *Craw, const double *sb, double *wadj, hipStream_t st) {
+    hipLaunchKernelGGL(k_round_prep, dim3((c.n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c.n, c.adj_ptr, c.adj_col,
+                       c.adj_slot, Craw, sb, wadj);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_round_proj(const DevCone &c, const double *X, int T, const double *dirT, unsigned long long *bits,
+                      hipStream_t st) {
+    const int W = T / 64;
+    hipLaunchKernelGGL(k_round_proj, dim3((c.n + kRoundRows - 1) / kRoundRows, (W + kRoundWords - 1) / kRoundWords),
+                       dim3(kBlock), 0, st, c.n, c.r, c.ld, T, X, dirT, bits);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_round_value(const DevCone &c, int T, const double *wadj, const unsigned long long *bits, double *part,
+                       double *values, hipStream_t st) {
+    const int rows = round_chunk_rows(c.n), nch = round_chunks(c.n);
+    hipLaunchKernelGGL(k_round_value, dim3((nch + kBlock / 64 - 1) / (kBlock / 64), T / 64), dim3(kBlock), 0, st, c.n,
+                       rows, nch, c.adj_ptr, c.adj_low, c.adj_col, wadj, bits, part);
+    LRS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_round_fin, dim3((T + kBlock - 1) / kBlock), dim3(kBlock), 0, st, T, nch, part, values);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_round_descent(const DevCone &c, int T, const double *wadj, unsigned long long *bits, int max_sweeps,
+                         int *sweeps, hipStream_t st) {
+    hipLaunchKernelGGL(k_round_descent, dim3(T / 64), dim3(64), 0, st, c.n, (int)c.adj_nnz, c.adj_ptr, c.adj_col, wadj,
+                       bits, max_sweeps, sweeps);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace lrs

@@ -173,6 +173,11 @@ struct lrs_ctx {
         double *Y = nullptr;       // restart coefficients (ncv x kk)
     };
     std::vector<LzWork> lz;
+    // sign rounding (lrs_round_signs): one buffer holding the sign words, the
+    // value partials, the values, the directions, sqrt(b), the adjacency weights and the sweep
+    // counts; allocated on first use, grown when a call needs more, freed with the context
+    void *round_buf = nullptr;
+    size_t round_bytes = 0;
     double *d_sendvec = nullptr;   // sharded: packed send rows of one Lanczos vector
     long sendvec_len = 0;
     // initial point cache (device layout, host copy) for the ranks it was drawn at
@@ -3040,7 +3045,7 @@ void lrs_ctx_destroy(lrs_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     delete c->comm;
     for (void *q : {(void *)c->s_tickets, (void *)c->s_tmpfin, (void *)c->s_rpart, (void *)c->s_fin, (void *)c->d_sendbuf,
-                    (void *)c->d_sendvec, (void *)c->Cw0, (void *)c->Craw0, (void *)c->xwg_snap})
+                    (void *)c->d_sendvec, (void *)c->Cw0, (void *)c->Craw0, (void *)c->xwg_snap, c->round_buf})
         if (q) (void)hipFree(q);
     for (int *q : c->d_send_rows)
         if (q) (void)hipFree(q);
@@ -3527,6 +3532,167 @@ int lrs_op_gram(lrs_ctx *c, int cone, int which, double *gram) {
     if (which == LRS_R) { if (gram_of(c, cone, c->W.R, nullptr, 0, g)) return -1; }
     else { if (gram_of(c, cone, c->W.U, c->W.V, 1, g)) return -1; }
     memcpy(gram, g.data(), sizeof(double) * g.size());
+    return 0;
+}
+
+// ---- sign rounding of a factor (no reference counterpart)
+// splitmix64's output function on the state x + golden gamma
+static inline unsigned long long round_mix(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+// The documented generator: element (c, t) from h = mix(mix(seed) ^ (t 2^32 + c)), a = mix(h),
+// b = mix(a), u1 = ((a >> 11) + 1) 2^-53 in (0, 1], u2 = (b >> 11) 2^-53 in [0, 1),
+// g = sqrt(-2 ln u1) cos(2 pi u2) (Box-Muller's cosine branch).
+static void round_dirs_fill(unsigned long long seed, int r, int trials, double *out) {
+    const unsigned long long s = round_mix(seed);
+    for (int t = 0; t < trials; ++t)
+        for (int q = 0; q < r; ++q) {
+            const unsigned long long h = round_mix(s ^ (((unsigned long long)t << 32) + (unsigned long long)q));
+            const unsigned long long a = round_mix(h), b = round_mix(a);
+            const double u1 = (double)((a >> 11) + 1) * 0x1p-53, u2 = (double)(b >> 11) * 0x1p-53;
+            out[q + (size_t)r * t] = std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586 * u2);
+        }
+}
+int lrs_round_dirs(unsigned long long seed, int r, int trials, double *out) {
+    LRS_NEED_ARG(out);
+    if (r < 1 || trials < 1) { set_err("lrs_round_dirs: r = %d, trials = %d (both >= 1)", r, trials); return -1; }
+    round_dirs_fill(seed, r, trials, out);
+    return 0;
+}
+
+// Whether cone k is a diagonally constrained cone of its own: n consecutive constraints o .. o +
+// n - 1, constraint o + i being the single entry (i, i) of this cone and touching no other cone,
+// and no other constraint in the cone.  sb[i] = sqrt(b_i / a_i) (a_i the entry's coefficient, 1 in
+// MaxCut).  Returns 0, or the refusal's code with the message set.
+static int round_qualify(lrs_ctx *c, int k, std::vector<double> &sb) {
+    const HostCone &hc = c->hp.cones[k];
+    const int n = hc.n;
+    if ((int)hc.ent.size() != n || n < 1) {
+        set_err("lrs_round_signs: cone %d is not diagonally constrained (%zu constraint entries on %d rows; "
+                "X_ii = b_i for every i and nothing else is required)", k, hc.ent.size(), n);
+        return -7;
+    }
+    const int o = hc.ent[0].con;
+    for (int i = 0; i < n; ++i) {
+        const HostEntry &e = hc.ent[i];
+        if (e.con != o + i || hc.prow[e.slot] != i || hc.pcol[e.slot] != i) {
+            set_err("lrs_round_signs: cone %d is not diagonally constrained (constraint %d is not the single entry "
+                    "(%d, %d))", k, e.con + 1, i + 1, i + 1);
+            return -7;
+        }
+    }
+    for (int k2 = 0; k2 < c->hp.K; ++k2) {
+        if (k2 == k) continue;
+        const HostCone &oc = c->hp.cones[k2];
+        auto hit = [&](int con) { return con >= o && con < o + n; };
+        bool shared = false;
+        for (const HostEntry &e : oc.ent) shared = shared || hit(e.con);
+        for (int con : oc.dense_con) shared = shared || hit(con);
+        for (int con : oc.r_con) shared = shared || hit(con);
+        if (shared) {
+            set_err("lrs_round_signs: cone %d is not diagonally constrained on its own (cone %d has entries in its "
+                    "constraints, so rounding the cone alone is not feasible)", k, k2);
+            return -7;
+        }
+    }
+    sb.resize(n);
+    for (int i = 0; i < n; ++i) {
+        const double v = c->hp.b[o + i] / hc.ent[i].a;
+        if (!(v > 0.0)) {
+            set_err("lrs_round_signs: cone %d, row %d: b_i = %g on coefficient %g (every X_ii must be > 0)", k, i + 1,
+                    c->hp.b[o + i], hc.ent[i].a);
+            return -8;
+        }
+        sb[i] = std::sqrt(v);
+    }
+    return 0;
+}
+
+int lrs_round_signs(lrs_ctx *c, int cone, int which, int trials, const double *dirs, unsigned long long seed,
+                    int local_search, int max_sweeps, double *values, unsigned long long *bits, int *best_trial,
+                    double *best_value, signed char *best_x, int *sweeps) {
+    LRS_NEED_LOADED(c);
+    if (trials < 64 || trials > 4096 || trials % 64 != 0) {
+        set_err("lrs_round_signs: trials = %d (a multiple of 64, 64 .. 4096)", trials);
+        return -2;
+    }
+    if (sharded(c)) { set_err("lrs_round_signs: sharded contexts are not supported"); return -3; }
+    if (cone < 0 || cone >= c->dp.K) { set_err("lrs_round_signs: cone %d of %d", cone, c->dp.K); return -4; }
+    if (is_lp(c, cone)) { set_err("lrs_round_signs: cone %d is the LP block", cone); return -5; }
+    if (!c->walloc) { set_err("lrs_round_signs: no solver state (ranks not set)"); return -6; }
+    if (which < LRS_R || which > LRS_V) { set_err("lrs_round_signs: factor %d (LRS_R .. LRS_V)", which); return -11; }
+    const DevCone &dc = c->dp.cones[cone];
+    if (dc.dense_c) {
+        set_err("lrs_round_signs: cone %d keeps a %s objective out of the slots", cone, dc.dense_c == 2 ? "constant" : "dense");
+        return -9;
+    }
+    if (dc.kd || dc.rp) { set_err("lrs_round_signs: cone %d has dense or rank-one constraint matrices", cone); return -10; }
+    std::vector<double> sb;
+    if (int rc = round_qualify(c, cone, sb)) return rc;
+    if (max_sweeps <= 0) max_sweeps = 50;
+    const int n = dc.n, r = dc.r, T = trials, W = T / 64, nch = round_chunks(n);
+    // the workspace: every piece 256-byte aligned in one allocation
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_bits = 0, o_part = o_bits + al(sizeof(double) * (size_t)W * n),
+                 o_val = o_part + al(sizeof(double) * (size_t)T * nch), o_dir = o_val + al(sizeof(double) * T),
+                 o_sb = o_dir + al(sizeof(double) * (size_t)r * T), o_w = o_sb + al(sizeof(double) * n),
+                 o_sw = o_w + al(sizeof(double) * (size_t)std::max(1L, dc.adj_nnz)), total = o_sw + al(sizeof(int) * W);
+    if (total > c->round_bytes) {
+        HIPC(hipStreamSynchronize(c->st));
+        if (c->round_buf) (void)hipFree(c->round_buf);
+        c->round_buf = nullptr;
+        c->round_bytes = 0;
+        HIPC(hipMalloc(&c->round_buf, total));
+        c->round_bytes = total;
+    }
+    char *base = (char *)c->round_buf;
+    unsigned long long *d_bits = (unsigned long long *)(base + o_bits);
+    double *d_part = (double *)(base + o_part), *d_val = (double *)(base + o_val), *d_dir = (double *)(base + o_dir),
+           *d_sb = (double *)(base + o_sb), *d_w = (double *)(base + o_w);
+    int *d_sw = (int *)(base + o_sw);
+    {   // directions, transposed to r x T row-major (a trial a lane: consecutive trials consecutive)
+        std::vector<double> gen, dT((size_t)r * T);
+        if (!dirs) {
+            gen.resize((size_t)r * T);
+            round_dirs_fill(seed, r, T, gen.data());
+            dirs = gen.data();
+        }
+        for (int t = 0; t < T; ++t)
+            for (int q = 0; q < r; ++q) dT[(size_t)q * T + t] = dirs[q + (size_t)r * t];
+        HIPC(h2d_sync(c, d_dir, dT.data(), sizeof(double) * dT.size()));
+        HIPC(h2d_sync(c, d_sb, sb.data(), sizeof(double) * n));
+    }
+    // C in the instance file's units: the slot values as loaded, before a reopt round's scaling
+    const double *Craw = c->c_scaled ? c->Craw0 : c->dp.Craw;
+    OPC(launch_round_prep(dc, Craw, d_sb, d_w, c->st));
+    OPC(launch_round_proj(dc, factor_ptr(c, which) + dc.foff, T, d_dir, d_bits, c->st));
+    int sw = 0;
+    std::vector<int> hsw(W, 0);
+    if (local_search) {
+        OPC(launch_round_descent(dc, T, d_w, d_bits, max_sweeps, d_sw, c->st));
+        HIPC(hipMemcpyAsync(hsw.data(), d_sw, sizeof(int) * W, hipMemcpyDeviceToHost, c->st));
+    }
+    OPC(launch_round_value(dc, T, d_w, d_bits, d_part, d_val, c->st));
+    std::vector<double> hv(T);
+    HIPC(hipMemcpyAsync(hv.data(), d_val, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    HIPC(hipStreamSynchronize(c->st));
+    for (int w = 0; w < W; ++w) sw = std::max(sw, hsw[w]);
+    int bt = 0;
+    for (int t = 1; t < T; ++t)
+        if (hv[t] < hv[bt]) bt = t;   // the smallest value, the lowest index on ties
+    if (values) memcpy(values, hv.data(), sizeof(double) * T);
+    if (bits) HIPC(hipMemcpy(bits, d_bits, sizeof(unsigned long long) * (size_t)W * n, hipMemcpyDeviceToHost));
+    if (best_x) {
+        std::vector<unsigned long long> col(n);
+        HIPC(hipMemcpy(col.data(), d_bits + (size_t)(bt / 64) * n, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) best_x[i] = ((col[i] >> (bt % 64)) & 1ull) ? 1 : -1;
+    }
+    if (best_trial) *best_trial = bt;
+    if (best_value) *best_value = hv[bt];
+    if (sweeps) *sweeps = sw;
     return 0;
 }
 

@@ -9,12 +9,18 @@
 // `--batch FILE` solves many instances in this one process (lrs_solve_batch): each non-empty
 // line of FILE is `<instance.dat-s> <jsonfile> [flags...]`, the line's flags parsed by the same
 // table on top of the command line's.  Exit code 1 if any instance failed (named on stderr).
+// `--roundTrials T` (a multiple of 64; default 0 = off) rounds the solve's R to +-1 assignments
+// (lrs_round_signs) when every cone is diagonally constrained: `--roundSeed S`
+// (default 0), `--roundLocalSearch 0|1` (default 1), `--roundFile PATH` (the best assignment, one
+// +1 / -1 a line in cone order); the JSON gains a "rounding" object.  A problem that does not
+// qualify keeps its output as it is, with one line on stderr.
 #include <getopt.h>
 
 #include <cctype>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 #include <string>
 #include <vector>
 
@@ -60,6 +66,9 @@ struct Flags {
     lrs_params p;
     std::string logFile, jsonFile, schedFile, batchFile;
     int device = 0;
+    int roundTrials = 0, roundLocalSearch = 1;
+    unsigned long long roundSeed = 0;
+    std::string roundFile;
 };
 static void parse_flags(int argc, char **argv, Flags &F) {
     lrs_params &p = F.p;
@@ -80,7 +89,9 @@ static void parse_flags(int argc, char **argv, Flags &F) {
         {"oracleRankNaive", no_argument, 0, 1021},
         {"rankSchedule", required_argument, 0, 2000}, {"nearStallFactor", required_argument, 0, 2001},
         {"disableOracle", no_argument, 0, 2002}, {"device", required_argument, 0, 2003},
-        {"quiet", no_argument, 0, 2004}, {"batch", required_argument, 0, 2005}, {0, 0, 0, 0}};
+        {"quiet", no_argument, 0, 2004}, {"batch", required_argument, 0, 2005},
+        {"roundTrials", required_argument, 0, 2006}, {"roundSeed", required_argument, 0, 2007},
+        {"roundLocalSearch", required_argument, 0, 2008}, {"roundFile", required_argument, 0, 2009}, {0, 0, 0, 0}};
     int opt, li = 0;
     optind = 0;   // a fresh scan (one per manifest line)
     while ((opt = getopt_long(argc, argv, "r:", opts, &li)) != -1) {
@@ -118,6 +129,10 @@ static void parse_flags(int argc, char **argv, Flags &F) {
         case 2003: F.device = atoi(optarg); break;
         case 2004: p.verbose = 0; break;
         case 2005: F.batchFile = optarg; break;
+        case 2006: F.roundTrials = atoi(optarg); break;
+        case 2007: F.roundSeed = strtoull(optarg, nullptr, 10); break;
+        case 2008: F.roundLocalSearch = atoi(optarg); break;
+        case 2009: F.roundFile = optarg; break;
         default: break;   // unknown flags: getopt already printed a message; ignored like main.c
         }
     }
@@ -137,6 +152,77 @@ static void finish_flags(Flags &F, std::vector<int> &sched) {
         fprintf(stderr, "[lrsdp] lbfgsListLength %d < 1; using 2\n", p.lbfgsListLength);
         p.lbfgsListLength = 2;
     }
+}
+
+// --roundTrials T after a solve: every cone's R rounded on the context's own stream (per cone the
+// same seed), the best values summed (cones with only diagonal constraints are independent).  On
+// success the JSON at jsonFile (if any) gains "rounding" before its closing brace and roundFile
+// receives the assignment; a cone that does not qualify leaves both as they are (one stderr line).
+static void round_and_report(lrs_ctx *ctx, const Flags &F, const char *jsonFile) {
+    if (F.roundTrials <= 0) return;
+    int K = 0;
+    lrs_problem_info(ctx, nullptr, &K, nullptr, nullptr, nullptr);
+    std::vector<int> dims(K > 0 ? K : 1);
+    lrs_problem_info(ctx, nullptr, nullptr, dims.data(), nullptr, nullptr);
+    std::vector<signed char> x;
+    std::vector<int> best(K, 0);
+    double value = 0.0, secs = 0.0;
+    int sweeps = 0;
+    for (int k = 0; k < K; ++k) {
+        std::vector<signed char> xk(dims[k] > 0 ? dims[k] : 1);
+        double v = 0.0;
+        int sw = 0;
+        lrs_sync(ctx);
+        timespec t0, t1;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        const int rc = lrs_round_signs(ctx, k, LRS_R, F.roundTrials, nullptr, F.roundSeed, F.roundLocalSearch, 0, nullptr,
+                                       nullptr, &best[k], &v, xk.data(), &sw);
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        if (rc) {
+            fprintf(stderr, "[lrsdp] rounding skipped: %s\n", lrs_last_error());
+            return;
+        }
+        secs += (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+        value += v;
+        sweeps = sw > sweeps ? sw : sweeps;
+        x.insert(x.end(), xk.begin(), xk.begin() + dims[k]);
+    }
+    std::string bt = K == 1 ? std::to_string(best[0]) : "[";
+    for (int k = 0; K != 1 && k < K; ++k) bt += (k ? ", " : "") + std::to_string(best[k]);
+    if (K != 1) bt += "]";
+    printf("Rounding: %d trials, seed %llu, local search %d: value %.10e (sweeps %d, %f s)\n", F.roundTrials, F.roundSeed,
+           F.roundLocalSearch ? 1 : 0, value, sweeps, secs);
+    if (!F.roundFile.empty()) {
+        FILE *f = fopen(F.roundFile.c_str(), "w");
+        if (!f) fprintf(stderr, "[lrsdp] cannot open %s\n", F.roundFile.c_str());
+        else {
+            for (signed char s : x) fprintf(f, "%d\n", (int)s);
+            fclose(f);
+        }
+    }
+    if (!jsonFile) return;
+    // lrs_write_json's text ends with the top-level closing brace: the object goes in before it
+    FILE *f = fopen(jsonFile, "rb");
+    if (!f) return;
+    std::string s;
+    char buf[4096];
+    size_t nr;
+    while ((nr = fread(buf, 1, sizeof(buf), f)) > 0) s.append(buf, nr);
+    fclose(f);
+    const size_t close = s.find_last_of('}');
+    if (close == std::string::npos) return;
+    size_t end = close;
+    while (end > 0 && isspace((unsigned char)s[end - 1])) end--;
+    char obj[512];
+    snprintf(obj, sizeof(obj),
+             ",\n  \"rounding\": {\n    \"trials\": %d,\n    \"seed\": %llu,\n    \"local_search\": %d,\n"
+             "    \"value\": %.16e,\n    \"best_trial\": %s,\n    \"sweeps\": %d,\n    \"time_sec\": %.16e\n  }\n}\n",
+             F.roundTrials, F.roundSeed, F.roundLocalSearch ? 1 : 0, value, bt.c_str(), sweeps, secs);
+    s = s.substr(0, end) + obj;
+    f = fopen(jsonFile, "wb");
+    if (!f) return;
+    fwrite(s.data(), 1, s.size(), f);
+    fclose(f);
 }
 
 // --batch FILE: load every line's instance, one lrs_solve_batch, one JSON each
@@ -244,6 +330,7 @@ static int run_batch(const Flags &base, const char *prog) {
             }
             printf("%s: pObj %10.6e dObj %10.6e ALM inner %ld ADMM %ld all_time %f -> %s\n", pid.c_str(), res[q].pobj,
                    res[q].dobj, res[q].alm_inner, res[q].admm_iter, res[q].solve_time, j->F.jsonFile.c_str());
+            round_and_report(j->ctx, j->F, j->F.jsonFile.c_str());   // each member on its own stream
         }
         long launches = 0, served = 0, alone = 0;
         int widest = 0;
@@ -334,6 +421,7 @@ int main(int argc, char **argv) {
         else
             printf("JSON output written to: %s\n", jsonFile);
     }
+    round_and_report(ctx, F, jsonFile);
     lrs_ctx_destroy(ctx);
     return 0;
 }

@@ -165,6 +165,9 @@ def load_library(path=None):
         "lrs_op_admm_round": (C.c_int, [vp, C.POINTER(vp), C.c_int, dp, dp, C.c_int]),
         "lrs_op_admm_rhs": (C.c_int, [vp, C.c_int, dp]),
         "lrs_admm_form": (C.c_int, [vp, ip, ip]),
+        "lrs_round_dirs": (C.c_int, [C.c_ulonglong, C.c_int, C.c_int, dp]),
+        "lrs_round_signs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, C.c_ulonglong, C.c_int, C.c_int, dp,
+                                      C.POINTER(C.c_ulonglong), ip, dp, C.POINTER(C.c_byte), ip]),
         "lrs_shard_plan": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_long), ip, ip, ip, ip, ip, ip, ip]),
     }
     for name, (res, args) in sig.items():
@@ -208,6 +211,25 @@ def comm_unique_id():
     if lib.lrs_comm_unique_id(buf) != 0:
         raise RuntimeError(f"comm_unique_id: {lib.lrs_last_error().decode()}")
     return buf.raw
+
+
+class RoundError(RuntimeError):
+    """A refused Solver.round_signs: `code` is lrs_round_signs' negative return value."""
+
+    def __init__(self, code, msg):
+        super().__init__(f"round_signs ({code}): {msg}")
+        self.code = code
+        self.message = msg
+
+
+def round_dirs(seed, r, trials):
+    """The seeded hyperplane normals of Solver.round_signs as an (r, trials) array (host only:
+    lrs_round_dirs, splitmix64 of (seed, trial, column) then Box-Muller)."""
+    lib = load_library()
+    out = np.empty((int(trials), int(r)))
+    if lib.lrs_round_dirs(int(seed), int(r), int(trials), _dptr(out)) != 0:
+        raise RuntimeError(f"round_dirs: {lib.lrs_last_error().decode()}")
+    return np.ascontiguousarray(out.T)
 
 
 class LoopbackGroup:
@@ -469,6 +491,35 @@ class Solver:
         g = np.empty(r * r)
         self._check(self.lib.lrs_op_gram(self.ctx, cone, which, _dptr(g)), "gram")
         return g.reshape(r, r)
+
+    # ---- sign rounding (include/lrsdp.h lrs_round_signs)
+    def round_signs(self, trials, seed=0, dirs=None, local_search=True, max_sweeps=50, cone=0, which=R):
+        """Round factor `which` of a diagonally constrained cone to `trials` +-1 assignments on
+        the device.  dirs: (r, trials) array of hyperplane normals, or None for round_dirs(seed,
+        r, trials).  Returns values (trials,), bits (trials // 64, n) uint64 (bit t of bits[w, i]
+        set: row i of trial 64 w + t is +1), best_trial, best_value, x (n,) int8 of +-1, sweeps.
+        A refusal raises RoundError with the library's negative code."""
+        trials = int(trials)
+        n = self.dims[cone] if 0 <= cone < len(self.dims) else 1
+        nw = max(1, trials // 64)
+        d = None
+        if dirs is not None:
+            r = self.get_rank()[cone]
+            d = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64).T)   # column-major r x trials
+            if d.shape != (trials, r):
+                raise ValueError(f"dirs: expected shape ({r}, {trials})")
+        values = np.empty(max(1, trials))
+        bits = np.zeros((nw, max(1, n)), dtype=np.uint64)
+        x = np.zeros(max(1, n), dtype=np.int8)
+        bt, sw, bv = C.c_int(), C.c_int(), C.c_double()
+        rc = self.lib.lrs_round_signs(self.ctx, cone, which, trials, _dptr(d) if d is not None else None,
+                                      int(seed), 1 if local_search else 0, int(max_sweeps), _dptr(values),
+                                      bits.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(bt), C.byref(bv),
+                                      x.ctypes.data_as(C.POINTER(C.c_byte)), C.byref(sw))
+        if rc != 0:
+            raise RoundError(rc, self.lib.lrs_last_error().decode())
+        return {"values": values[:trials], "bits": bits, "best_trial": bt.value, "best_value": bv.value, "x": x[:n],
+                "sweeps": sw.value}
 
     # ---- solves
     def solve(self, **kw):
@@ -951,8 +1002,9 @@ def run_lorads_batch(jobs, params, near_stall_factor=0.7, timeout=3600, device=0
 
 
 def run_lorads(instance_path, json_output_path, params, fixed_rank=None, rank_schedule_path=None,
-               near_stall_factor=0.7, timeout=3600, device=0):
-    """Same contract as benchmark.py:219-285, on the MI355X binary."""
+               near_stall_factor=0.7, timeout=3600, device=0, round_trials=None):
+    """Same contract as benchmark.py:219-285, on the MI355X binary.  round_trials (a multiple of
+    64): passed through as --roundTrials, the JSON then carries a "rounding" object."""
     if not BIN_PATH.exists():
         raise RuntimeError(f"binary not built: {BIN_PATH}")
     json_output_path = Path(json_output_path)
@@ -967,6 +1019,8 @@ def run_lorads(instance_path, json_output_path, params, fixed_rank=None, rank_sc
         cmd += ["--rankSchedule", str(rank_schedule_path), "--nearStallFactor", str(near_stall_factor)]
     elif fixed_rank is not None:
         cmd += ["--fixedRank", str(fixed_rank)]
+    if round_trials:
+        cmd += ["--roundTrials", str(int(round_trials))]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
         if r.returncode != 0:
