@@ -156,6 +156,11 @@ __device__ __forceinline__ gdouble *held_gs(double *p) {
     asm volatile("" : "+s"(p));
     return (gdouble *)p;
 }
+// The build preloads every kernel's leading arguments into scalar registers at wave launch
+// (Makefile KFLAGS).  A kernel that is short of scalar registers takes this empty struct as its
+// first parameter: a by-value struct is passed by reference, and preloading stops at the first
+// such argument, so the kernel loads its arguments where it uses them, as before.
+struct NoPreload {};
 
 // Sum over an aligned group of G lanes; every lane of the group gets the same value.
 template <int G>
@@ -2801,6 +2806,20 @@ constexpr int kLatMaxPartials = 256;             // producer blocks one control 
 constexpr int kSliceA = 2;                       // lower entries per lane group in a dense-row slice of A
 constexpr int kSliceB = 4;                       // entries per lane group in a dense-row slice of B
 
+// The latency kernels' small integers in one argument word, so that what a wave needs before its
+// first vector load fits the 14 argument dwords that are preloaded into scalar registers at wave
+// launch: row waves (<= 7), row blocks and up to two partial-block counts (each <= kLatMaxPartials)
+constexpr int kLatPkW = 4, kLatPkN = 9;
+static_assert(kLatRowWaves < (1 << kLatPkW) && kLatMaxPartials < (1 << kLatPkN) && kLatPkW + 3 * kLatPkN <= 31,
+              "packed latency-kernel word");
+__host__ __device__ __forceinline__ int lat_pk(int lrw, int nrb, int n1, int n2) {
+    return lrw | (nrb << kLatPkW) | (n1 << (kLatPkW + kLatPkN)) | (n2 << (kLatPkW + 2 * kLatPkN));
+}
+__device__ __forceinline__ int lat_pk_lrw(int pk) { return pk & ((1 << kLatPkW) - 1); }
+__device__ __forceinline__ int lat_pk_nrb(int pk) { return (pk >> kLatPkW) & ((1 << kLatPkN) - 1); }
+__device__ __forceinline__ int lat_pk_n1(int pk) { return (pk >> (kLatPkW + kLatPkN)) & ((1 << kLatPkN) - 1); }
+__device__ __forceinline__ int lat_pk_n2(int pk) { return (pk >> (kLatPkW + 2 * kLatPkN)) & ((1 << kLatPkN) - 1); }
+
 // control wave: NV partial vectors summed over 1 <= nblk <= kLatMaxPartials producer blocks
 // (lane l takes blocks l, l+64, ...).  Split in two so that the loads can be issued first
 // thing in the kernel (clamped, not branched): the wave then waits for one memory trip.
@@ -2863,28 +2882,35 @@ __device__ __forceinline__ void wave_reduce_partials(const double *__restrict__ 
 // PLAIN: as in k_lat_b below.
 template <int G, int E, int NO, bool PLAIN = false, bool TS = false>
 __global__ void __launch_bounds__(kLatNT) k_lat_a(
-    int n, int ld, long foff, const int *__restrict__ adj_ptr, const int *__restrict__ adj_low,
-    const int *__restrict__ adj_col, const int *__restrict__ adj_slot, const double *__restrict__ Cw,
-    const double *__restrict__ Rb0, const double *__restrict__ Rb1, double *__restrict__ Dall,
-    const double *__restrict__ G0, const double *__restrict__ G1, const double *__restrict__ s0a,
-    const double *__restrict__ y0a, const double *__restrict__ s1a, const double *__restrict__ y1a,
-    double *__restrict__ uRD, double *__restrict__ uDD, const int *__restrict__ loc_ptr,
-    const int *__restrict__ loc_con, const double *__restrict__ loc_w, const double2 *__restrict__ loc1,
-    const double *__restrict__ b, double *__restrict__ cvs, const double *__restrict__ lam,
-    double *__restrict__ rec, int do_glob, int mg, const int *__restrict__ glob, int m, int K,
-    const int *__restrict__ con_ptr, const int *__restrict__ con_slot, const double *__restrict__ con_w,
-    const double *__restrict__ uRR, const double *__restrict__ par, const double *__restrict__ ctrl_prev,
-    double *__restrict__ ctrl_cur, const double *__restrict__ ls_prev, const double *__restrict__ partC, int nblkC,
-    double *__restrict__ partA, int pblk_off, int gwide, int nrb, int lrw, int nda, const int *__restrict__ dra) {
+    const double *__restrict__ partC, const double *__restrict__ ctrl_prev, const double *__restrict__ par,
+    const double *__restrict__ ls_prev, const int *__restrict__ adj_ptr, const int *__restrict__ adj_low, int n,
+    int pk, int ld, long foff, const int *__restrict__ adj_col, const int *__restrict__ adj_slot,
+    const double *__restrict__ Cw, const double *__restrict__ Rb0, const double *__restrict__ Rb1,
+    double *__restrict__ Dall, const double *__restrict__ G0, const double *__restrict__ G1,
+    const double *__restrict__ s0a, const double *__restrict__ y0a, const double *__restrict__ s1a,
+    const double *__restrict__ y1a, double *__restrict__ uRD, double *__restrict__ uDD,
+    const int *__restrict__ loc_ptr, const int *__restrict__ loc_con, const double *__restrict__ loc_w,
+    const double2 *__restrict__ loc1, const double *__restrict__ b, double *__restrict__ cvs,
+    const double *__restrict__ lam, double *__restrict__ rec, int do_glob, int mg, const int *__restrict__ glob, int m,
+    int K, const int *__restrict__ con_ptr, const int *__restrict__ con_slot, const double *__restrict__ con_w,
+    const double *__restrict__ uRR, double *__restrict__ ctrl_cur, double *__restrict__ partA, int pblk_off, int gwide,
+    int nda, const int *__restrict__ dra) {
     __shared__ double c[C_NCTRL];
     __shared__ double pl[P_NPAR];
     __shared__ double sred[10];   // TS: the control wave's totals
     LRS_TS(0, 0);
     LRS_BLK_BEGIN();
-    // lrw row waves + the control wave (an argument beside nrb, loaded in the first argument batch:
-    // blockDim.x would be one more load before the first branch)
+    // lrw row waves + the control wave (in the packed word of the preloaded arguments: blockDim.x
+    // would be a load before the first branch)
+    const int lrw = lat_pk_lrw(pk), nrb = lat_pk_nrb(pk), nblkC = lat_pk_n1(pk);
     const int nwv = lrw + 1, rpb = lrw * 64 / G;   // waves, rows of this block
     const bool ctrl_wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == nwv - 1;   // wave-uniform
+    // the control wave is the block's youngest wave and shares its SIMD with a row wave: raised
+    // until the barrier, it no longer loses the issue arbitration to that wave's address
+    // arithmetic (the launch waits for the control wave; -DLRS_NO_LAT_CTRL_PRIO: not raised)
+#ifndef LRS_NO_LAT_CTRL_PRIO
+    if (ctrl_wave) __builtin_amdgcn_s_setprio(3);
+#endif
     const int lane = threadIdx.x & (G - 1);
     // blocks [0, nrb): one row per lane group.  Blocks past nrb: slices of the dense rows --
     // every lane group of the block takes kSliceA consecutive lower entries of one dense row
@@ -2921,17 +2947,24 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
     }
     __builtin_amdgcn_sched_barrier(0);
     // this iteration's operands: ctrl_step folds the previous stage (and flips the G and R
-    // buffers) exactly when `fold` holds
-    const double lsflag = ls_prev[LS_FLAG];
-    const int fold = (ctrl_prev[C_ACT2] != 0.0 && ctrl_prev[C_PENDING] == 1.0 && lsflag == 0.0) ? 1 : 0;
+    // buffers) exactly when `fold` holds.  The control words and the operand bases of the
+    // prologue are wanted here, together: one batch of scalar loads, one trip, under the vector
+    // trip above (the compiler would sink every argument load to its first use, a trip each)
+    const double lsflag = ls_prev[LS_FLAG], lstau = ls_prev[LS_TAU];
+    const double cact2 = ctrl_prev[C_ACT2], cpend = ctrl_prev[C_PENDING];
+    const double crcur = ctrl_prev[C_RCUR], cgcur = ctrl_prev[C_GCUR];
+    asm volatile("" ::"s"(lsflag), "s"(lstau), "s"(cact2), "s"(cpend), "s"(crcur), "s"(cgcur), "s"(Rb0), "s"(Rb1),
+                 "s"(G0), "s"(G1), "s"(s0a), "s"(y0a), "s"(s1a), "s"(y1a), "s"(Dall), "s"(adj_col), "s"(adj_slot),
+                 "s"(Cw), "s"(loc1), "s"(b), "s"(cvs), "s"(lam), "s"(foff), "s"(ld), "s"(m));
+    const int fold = (cact2 != 0.0 && cpend == 1.0 && lsflag == 0.0) ? 1 : 0;
 #ifdef LRS_PHASE_TIMING
     // diagnostics: the row header (a vector load) and the control words (scalar loads) arrived
     if (blockIdx.x == 0 && threadIdx.x == 0 && kb != -12345) g_phase_tmp[0][10] = wall_clock64();
     if (blockIdx.x == 0 && threadIdx.x == 0 && fold != 12345) g_phase_tmp[0][9] = wall_clock64();
     if (blockIdx.x == 0 && ctrl_wave && (threadIdx.x & 63) == 0 && ccv != 12345.678) g_phase_tmp[0][11] = wall_clock64();
 #endif
-    const bool r1 = (ctrl_prev[C_RCUR] != 0.0) != (fold != 0);
-    const bool g1 = (ctrl_prev[C_GCUR] != 0.0) != (fold != 0);
+    const bool r1 = (crcur != 0.0) != (fold != 0);
+    const bool g1 = (cgcur != 0.0) != (fold != 0);
     const double *__restrict__ R = (r1 ? Rb1 : Rb0) + foff;
     const double *__restrict__ Gc = (g1 ? G1 : G0) + foff;
     const double *__restrict__ s0 = s0a + foff, *__restrict__ y0 = y0a + foff;
@@ -2980,7 +3013,7 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
             for (int q = 0; q < C_NCTRL; ++q) cr[q] = c[q];
 #pragma unroll
             for (int q = 0; q < P_NPAR; ++q) pr[q] = pl[q];
-            ctrl_step(cr, pr, lsflag, ls_prev[LS_TAU], fold, s, mg == 0);
+            ctrl_step(cr, pr, lsflag, lstau, fold, s, mg == 0);
             if (l64 == 0) {
 #pragma unroll
                 for (int q = 0; q < C_NCTRL; ++q) c[q] = cr[q];
@@ -3066,6 +3099,9 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
         // constraints' loop below, adds nothing
         nwh = held_s(nwv | (TS && ctrl_wave && !fgl ? kLatZeroBit : 0));
     }
+#ifndef LRS_NO_LAT_CTRL_PRIO
+    __builtin_amdgcn_s_setprio(0);
+#endif
     __syncthreads();
     LRS_TS(0, 3);
     // (PLAIN: the control block published behind the row stores, or at once when the launch ends here)
@@ -3312,17 +3348,16 @@ __global__ void __launch_bounds__(kLatNT) k_lat_a(
 // acknowledgement behind the first store of a row within the prefetch window.
 template <int G, int E, int NO, bool PLAIN = false, bool TS = false>
 __global__ void __launch_bounds__(kLatNT) k_lat_b(
-    int n, int ld, long foff, const int *__restrict__ adj_ptr, const int *__restrict__ adj_low,
-    const int *__restrict__ adj_col, const int *__restrict__ adj_slot, double *Rb0, double *Rb1,
+    const double *__restrict__ partA, const double *__restrict__ partB, const double *__restrict__ ctrl,
+    const double *__restrict__ par, const int *__restrict__ adj_ptr, const int *__restrict__ adj_low, int n, int pk,
+    int ld, long foff, const int *__restrict__ adj_col, const int *__restrict__ adj_slot, double *Rb0, double *Rb1,
     const double *__restrict__ Dall, double *G0, double *G1, double *s0, double *y0, double *s1, double *y1,
     double *__restrict__ uRR, const double *__restrict__ Craw, const int *__restrict__ slot_ptr,
     const int *__restrict__ slot_con, const double *__restrict__ slot_a, const double2 *__restrict__ slot1,
     const double *__restrict__ rec, const int *__restrict__ loc_ptr, const int *__restrict__ loc_con,
     const double *__restrict__ loc_w, const double2 *__restrict__ loc1, const double *__restrict__ b,
-    double *__restrict__ cvs, const double *__restrict__ par, const double *__restrict__ ctrl,
-    const double *__restrict__ partA, int nblkA, const double *__restrict__ partB, int nblkB,
-    double *__restrict__ ls_cur, int L, double *__restrict__ partC, int pblk_off, int m, double *hmirror,
-    double seq, int nrb, int lrw, int ndb, const int *__restrict__ drb, double *__restrict__ gl, double *CRb,
+    double *__restrict__ cvs, double *__restrict__ ls_cur, int L, double *__restrict__ partC, int pblk_off, int m,
+    double *hmirror, double seq, int ndb, const int *__restrict__ drb, double *__restrict__ gl, double *CRb,
     const double *__restrict__ CDb) {
     __shared__ double red[12];
     __shared__ double ls[LS_N];
@@ -3330,11 +3365,14 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
     __shared__ double gsh[kLatRows * E];   // slice blocks: the lane groups' partial gradients
     LRS_TS(2, 0);
     LRS_BLK_BEGIN();
-    mirror_ctrl(ctrl, hmirror, seq);
-    // lrw row waves + the control wave (an argument beside nrb, loaded in the first argument batch:
-    // blockDim.x would be one more load before the first branch)
+    // lrw row waves + the control wave (in the packed word of the preloaded arguments: blockDim.x
+    // would be a load before the first branch)
+    const int lrw = lat_pk_lrw(pk), nrb = lat_pk_nrb(pk), nblkA = lat_pk_n1(pk), nblkB = lat_pk_n2(pk);
     const int nwv = lrw + 1, rpb = lrw * 64 / G;   // waves, rows of this block
     const bool ctrl_wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == nwv - 1;   // wave-uniform
+#ifndef LRS_NO_LAT_CTRL_PRIO
+    if (ctrl_wave) __builtin_amdgcn_s_setprio(3);   // (as in k_lat_a, until the barrier)
+#endif
     const int lane = threadIdx.x & (G - 1);
     // blocks [0, nrb): one row per lane group.  Blocks past nrb: slices of the dense rows --
     // every lane group takes kSliceB consecutive entries of one dense row, the block's partial
@@ -3368,9 +3406,19 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
         ke = adj_ptr[ic + 1];
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (ctrl[C_ACT2] == 0.0) return;
-    const int gcur = (int)ctrl[C_GCUR], h = (int)ctrl[C_HEAD];
-    const bool r1 = ctrl[C_RCUR] != 0.0;
+    // the control words and the operand bases of the prologue, wanted here together: one batch
+    // of scalar loads, one trip, under the vector trip above (as in k_lat_a).  The batch-end
+    // mirror behind them, in front of the early return: only block 0's first wave takes it.
+    // (PLAIN only: the general instantiations spill scalar registers as it is, and more with it)
+    const double cact2 = ctrl[C_ACT2], cgcur = ctrl[C_GCUR], chead = ctrl[C_HEAD], crcur = ctrl[C_RCUR];
+    if constexpr (PLAIN)
+        asm volatile("" ::"s"(cact2), "s"(cgcur), "s"(chead), "s"(crcur), "s"(Rb0), "s"(Rb1), "s"(Dall), "s"(G0),
+                     "s"(G1), "s"(s0), "s"(y0), "s"(s1), "s"(y1), "s"(adj_col), "s"(adj_slot), "s"(Craw), "s"(slot1),
+                     "s"(loc1), "s"(rec), "s"(b), "s"(foff), "s"(ld), "s"(L), "s"(m), "s"(hmirror), "s"(seq));
+    mirror_ctrl(ctrl, hmirror, seq);
+    if (cact2 == 0.0) return;
+    const int gcur = (int)cgcur, h = (int)chead;
+    const bool r1 = crcur != 0.0;
     const double *__restrict__ R = (r1 ? Rb1 : Rb0) + foff;
     double *__restrict__ Rn = (r1 ? Rb0 : Rb1) + foff;
     const double *__restrict__ D = Dall + foff;
@@ -3532,6 +3580,9 @@ __global__ void __launch_bounds__(kLatNT) k_lat_b(
         // accumulators stay +0.0 -- the control wave has no row
         nwh = held_s(nwv | (TS && ctrl_wave ? kLatZeroBit : 0));
     }
+#ifndef LRS_NO_LAT_CTRL_PRIO
+    __builtin_amdgcn_s_setprio(0);
+#endif
     __syncthreads();
     LRS_TS(2, 2);
     // (PLAIN: the line search published behind the row stores, or at once when the launch ends here)
@@ -4316,7 +4367,7 @@ __global__ void __launch_bounds__(kRowBlock) k_wide_b(
 //   over its row's entries of the tile pair in column order, 16 columns at a time, into GP[x];
 // k_wide_bf sums the kNX partial rows in group order and runs the row epilogue.
 __global__ void __launch_bounds__(kRowBlock, 4) k_tile_b1(   // <= 128 VGPRs: two blocks a CU (68 KB LDS each)
-    int n, int r, int ld, long foff, int nitems, const int4 *__restrict__ items, const unsigned *__restrict__ pq,
+    NoPreload, int n, int r, int ld, long foff, int nitems, const int4 *__restrict__ items, const unsigned *__restrict__ pq,
     const int *__restrict__ tslot, const double *Rb0, const double *Rb1, double *__restrict__ uRR,
     double *__restrict__ Sv, const double *__restrict__ Craw, const int *__restrict__ slot_ptr,
     const int *__restrict__ slot_con, const double *__restrict__ slot_a, const double2 *__restrict__ slot1,
@@ -6744,14 +6795,11 @@ static bool lat_tsum() {
     const char *e = getenv("LRS_LAT_TSUM");
     return !(e && e[0] == '0');
 }
-// LRS_LAT_ROWWAVES = 1..7 forces the row waves per latency block (0: chosen per launch)
+// LRS_LAT_ROWWAVES = 1..7 forces the row waves per latency block (0: chosen per launch; read per
+// enqueue, as LRS_LAT_PLAIN: tests/test_gpu_lat_args.py)
 static int lat_forced_waves() {
-    static int forced = -1;
-    if (forced < 0) {
-        const char *e = getenv("LRS_LAT_ROWWAVES");
-        forced = e ? std::max(0, std::min(kLatRowWaves, atoi(e))) : 0;
-    }
-    return forced;
+    const char *e = getenv("LRS_LAT_ROWWAVES");
+    return e ? std::max(0, std::min(kLatRowWaves, atoi(e))) : 0;
 }
 
 // the multi-launch kernel family forced by lrs_set_kernel_path (4, the single-workgroup inner
@@ -7022,13 +7070,13 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
                        pstr)
         if (lat) {
 #define LRS_LAT_A(PL_, TS_)                                                                                    \
-    hipLaunchKernelGGL((k_lat_a<GG, EE, kLatNoA, PL_, TS_>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown, c.ld, c.foff,   \
-                       c.adj_ptr, c.adj_low, c.adj_col, c.adj_slot, P.Cw, W.R, W.R2, W.D, W.G[0], W.G[1], W.ls[0], \
-                       W.ly[0], W.ls[1], W.ly[1], W.uvt0, W.uvt1, P.loc_ptr, P.loc_con, P.loc_w,                 \
+    hipLaunchKernelGGL((k_lat_a<GG, EE, kLatNoA, PL_, TS_>), dim3(grid), dim3(lg[k].nt), 0, st, inC, ctrl_prev, W.par, \
+                       ls_prev, c.adj_ptr, c.adj_low, c.nown, lat_pk(lg[k].nt / 64 - 1, lg[k].nrb, nC, 0), c.ld,   \
+                       c.foff, c.adj_col, c.adj_slot, P.Cw, W.R, W.R2, W.D, W.G[0], W.G[1], W.ls[0], W.ly[0],      \
+                       W.ls[1], W.ly[1], W.uvt0, W.uvt1, P.loc_ptr, P.loc_con, P.loc_w,                           \
                        reinterpret_cast<const double2 *>(P.loc1), P.b, W.cvs, W.lam, W.rec, k == 0 ? 1 : 0, P.mg,   \
-                       P.glob, P.m, P.K, P.con_ptr, P.con_slot, P.con_w, W.uvt2, W.par, ctrl_prev, ctrl_cur,       \
-                       ls_prev, inC, nC, W.part, off, gwide, lg[k].nrb, lg[k].nt / 64 - 1, (int)c.dra_h.size(),    \
-                       c.dra)
+                       P.glob, P.m, P.K, P.con_ptr, P.con_slot, P.con_w, W.uvt2, ctrl_cur, W.part, off, gwide,     \
+                       (int)c.dra_h.size(), c.dra)
             const bool plain = lat_plain(P, c, lg[k]);
             LRS_LAYOUT_SWITCH(c.G, c.E, {
                 if (plain && tsum) LRS_LAT_A(true, true);
@@ -7130,14 +7178,14 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
         const bool small = pb[k].small;
         if (lat) {
 #define LRS_LAT_B(PL_, TS_)                                                                                    \
-    hipLaunchKernelGGL((k_lat_b<GG, EE, kLatNoB, PL_, TS_>), dim3(grid), dim3(lg[k].nt), 0, st, c.nown, c.ld, c.foff,   \
-                       c.adj_ptr, c.adj_low, c.adj_col, c.adj_slot, W.R, W.R2, W.D, W.G[0], W.G[1], W.ls[0],       \
-                       W.ly[0], W.ls[1], W.ly[1], W.uvt2, P.Craw, P.slot_ptr, P.slot_con, P.slot_a,               \
-                       reinterpret_cast<const double2 *>(P.slot1), W.rec, P.loc_ptr, P.loc_con, P.loc_w,           \
-                       reinterpret_cast<const double2 *>(P.loc1), P.b, W.cvs, W.par, ctrl_cur, inA, nA, W.partB,    \
-                       P.mg > 0 ? gg : 0, ls_cur, L, W.partC, off, P.m, k == 0 ? a.hmirror : nullptr, a.seq,        \
-                       lg[k].nrb, lg[k].nt / 64 - 1, (int)c.drb_h.size(), c.drb, W.gl + glo,                       \
-                       P.ndense ? W.CR : nullptr, W.CD)
+    hipLaunchKernelGGL((k_lat_b<GG, EE, kLatNoB, PL_, TS_>), dim3(grid), dim3(lg[k].nt), 0, st, inA, W.partB, ctrl_cur, \
+                       W.par, c.adj_ptr, c.adj_low, c.nown,                                                       \
+                       lat_pk(lg[k].nt / 64 - 1, lg[k].nrb, nA, P.mg > 0 ? gg : 0), c.ld, c.foff, c.adj_col,       \
+                       c.adj_slot, W.R, W.R2, W.D, W.G[0], W.G[1], W.ls[0], W.ly[0], W.ls[1], W.ly[1], W.uvt2,     \
+                       P.Craw, P.slot_ptr, P.slot_con, P.slot_a, reinterpret_cast<const double2 *>(P.slot1), W.rec, \
+                       P.loc_ptr, P.loc_con, P.loc_w, reinterpret_cast<const double2 *>(P.loc1), P.b, W.cvs,       \
+                       ls_cur, L, W.partC, off, P.m, k == 0 ? a.hmirror : nullptr, a.seq, (int)c.drb_h.size(),     \
+                       c.drb, W.gl + glo, P.ndense ? W.CR : nullptr, W.CD)
             const bool plain = lat_plain(P, c, lg[k]);
             LRS_LAYOUT_SWITCH(c.G, c.E, {
                 if (plain && tsum) LRS_LAT_B(true, true);
@@ -7189,7 +7237,7 @@ int enqueue_alm_stages(const AlmIterArgs &a, int parity, int mask, hipStream_t s
         if (tbt[k]) {
             static int rcb = 0;   // the resident blocks stride over the items (stage B 864 -> 803 us on C5)
             const int nwb = std::min(grid, resident_blocks(k_tile_b1, &rcb, kRowBlock));
-            hipLaunchKernelGGL(k_tile_b1, dim3(grid), dim3(kRowBlock), 0, st, c.n, c.r, c.ld, c.foff, c.sa_items,
+            hipLaunchKernelGGL(k_tile_b1, dim3(grid), dim3(kRowBlock), 0, st, NoPreload{}, c.n, c.r, c.ld, c.foff, c.sa_items,
                                reinterpret_cast<const int4 *>(c.sa_item), c.sa_pq, c.sa_slot, W.R, W.R2, W.uvt2,
                                c.sa_S - c.slot_off, P.Craw, P.slot_ptr,
                                P.slot_con, P.slot_a,
@@ -7962,7 +8010,7 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_alm(SmallArgs A) {
 // final control block also goes to mirror[b] (each thread re-reads the element it wrote), so the
 // host fetches a launch's control blocks in one copy.
 template <int LD, bool AL>
-__global__ void __launch_bounds__(kSmallThreads) k_small_alm_batch(const SmallArgs *__restrict__ tab,
+__global__ void __launch_bounds__(kSmallThreads) k_small_alm_batch(NoPreload, const SmallArgs *__restrict__ tab,
                                                                    double *__restrict__ mirror) {
     typedef const __attribute__((address_space(4))) SmallArgs CArgs;
     CArgs &A = *(CArgs *)(unsigned long long)(tab + blockIdx.x);
@@ -8183,7 +8231,7 @@ static int launch_small_batch_ld(const SmallArgs *tab, double *mirror, int nblk,
         }
         attr = true;
     }
-    hipLaunchKernelGGL((k_small_alm_batch<LD, AL>), dim3(nblk), dim3(kSmallThreads), lds, st, tab, mirror);
+    hipLaunchKernelGGL((k_small_alm_batch<LD, AL>), dim3(nblk), dim3(kSmallThreads), lds, st, NoPreload{}, tab, mirror);
     LRS_CHECK_LAUNCH();
     return 0;
 }
