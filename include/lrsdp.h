@@ -288,6 +288,36 @@ int lrs_round_dirs(unsigned long long seed, int r, int trials, double *out);
 int lrs_round_signs(lrs_ctx *ctx, int cone, int which, int trials, const double *dirs, unsigned long long seed,
                     int local_search, int max_sweeps, double *values, unsigned long long *bits, int *best_trial,
                     double *best_value, signed char *best_x, int *sweeps);
+/* ---- Triangle-inequality separation for diagonally constrained cones.  No
+ * reference counterpart.  For a cone that is diagonally constrained in lrs_round_signs' sense
+ * (X_ii = b_i / a_i for every i and nothing else, none of it touching another cone, every b_i / a_i
+ * > 0) and a factor X (n x r, `which` one of LRS_R .. LRS_V), x_ij = <X_i, X_j> / sqrt(b_i b_j)
+ * over the columns c < r, and for every i < j < k the four inequalities of the metric polytope
+ *   type 0: + x_ij + x_ik + x_jk >= -1      type 2: - x_ij + x_ik - x_jk >= -1
+ *   type 1: + x_ij - x_ik - x_jk >= -1      type 3: - x_ij - x_ik + x_jk >= -1
+ * have the violation v = -1 - ((s_ij x_ij + s_ik x_ik) + s_jk x_jk), summed in that order with the
+ * type's signs.  Of the inequalities with v > min_violation (>= 0) the call returns the max_cuts
+ * largest (1 .. LRS_TRI_MAX_K) under the strict total order v descending, then (i, j, k, type)
+ * ascending lexicographically, sorted in that order: cuts[t] = {i, j, k, type} (0-based) and
+ * violation[t], t < *n_cuts = min(max_cuts, *n_violated); *n_violated the exact number with v >
+ * min_violation; *max_violation the largest v (0 when none qualifies).  Every output may be NULL.
+ * The objective is not read (a dense or constant C is fine).  All of it runs on the device and the
+ * context's stream: the matrix x (kept as tri_pad(n)^2 doubles in a per-context workspace, hence n
+ * <= LRS_TRI_MAX_N), then scans of the 4 C(n, 3) inequalities: one that counts, as many as the
+ * radix select over the key (v, index) needs to bound the cut, one that collects.  Integer atomics
+ * only: every output is the same bits on every run.  A row of X need not have norm sqrt(b_i):
+ * x_ij is what the formula says.
+ * Refusals, each a negative code with its message in lrs_last_error() and nothing started: -2
+ * max_cuts outside 1 .. LRS_TRI_MAX_K, -3 a sharded context, -4 no such cone, -5 the LP block, -6
+ * ranks not set, -7 a cone that is not diagonally constrained, -8 a b_i <= 0, -10 dense or rank-one
+ * constraint matrices, -11 a selector other than LRS_R .. LRS_V, -12 min_violation negative or NaN,
+ * -13 n < 3, -14 n > LRS_TRI_MAX_N (-1: the header's general failures). */
+#define LRS_TRI_MAX_K 65536
+#define LRS_TRI_MAX_N 32768
+int lrs_separate_triangles(lrs_ctx *ctx, int cone, int which, int max_cuts, double min_violation,
+                           int *cuts /* [max_cuts][4]: i, j, k (0-based, i<j<k), type 0..3 */,
+                           double *violation /* [max_cuts] */, int *n_cuts,
+                           long long *n_violated, double *max_violation);
 /* trajectory (phase 1 then phase 2) after lrs_solve: curr and oracle ranks */
 int lrs_trajectory(lrs_ctx *ctx, int phase, int *curr_rank, int *oracle_rank, int cap);
 /* JSON like lorads_logging.c:618-712 */

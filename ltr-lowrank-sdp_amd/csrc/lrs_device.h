@@ -522,6 +522,27 @@ int launch_round_value(const DevCone &c, int T, const double *wadj, const unsign
 int launch_round_descent(const DevCone &c, int T, const double *wadj, unsigned long long *bits, int max_sweeps,
                          int *sweeps, hipStream_t st);
 
+// ---- triangle-inequality separation (lrs_kernels.hip "Triangle-inequality separation") ----
+// launch_tri_gram: x = D^-1/2 X X^T D^-1/2 of one cone (X its rows, n x ld; sb[n] = sqrt(b_i)) as a
+// full tri_pad(n)^2 matrix, zero past n.  launch_tri_scan: one pass over every i < j < k and type
+// with v > minv.  Its key is 128 bits: hi = ~bits(v), lo = ((i n + j) n + k) 4 + type.  mode 0:
+// gcnt[0] += the count, gcnt[1] = max bits(v), ghist[d] += the keys whose digit (hi >> shift) &
+// mask is d.  mode 1: the same histogram of part's (0: hi, 1: lo) digit over the keys with
+// (part >> pshift) == prefix (part 1: and hi == fixed_hi).  mode 2: the records {bits(v), lo} with
+// (part >> pshift) <= prefix (part 1: hi < fixed_hi, or equal and that) appended to rec[cap] at
+// *cursor, which keeps counting past cap.  The caller zeroes ghist, gcnt and cursor.
+constexpr int kTriTile = 32;      // tile edge of the scan (why not 64)
+constexpr int kTriBins = 4096;    // a radix digit is at most 12 bits
+struct TriPass {
+    unsigned long long prefix, fixed_hi;
+    int part, pshift, shift;
+    unsigned mask, cap;
+};
+int tri_pad(int n);
+int launch_tri_gram(const DevCone &c, const double *X, const double *sb, double *x, hipStream_t st);
+int launch_tri_scan(int mode, int n, double minv, const TriPass &P, const double *x, unsigned long long *ghist,
+                    unsigned long long *gcnt, unsigned *cursor, void *rec, hipStream_t st);
+
 // ---- dual infeasibility (Lanczos for lambda_min of S per cone) ----
 // y = S x over one cone's adjacency (S on the global slots, x / y cone-local vectors)
 int launch_symv(const DevProblem &P, int cone, const double *S, const double *x, double *y, hipStream_t st);

@@ -9883,4 +9883,180 @@ int launch_round_descent(const DevCone &c, int T, const double *wadj, unsigned l
     return 0;
 }
 
+// ------------------------------------------------------------------------
+// Triangle-inequality separation (no reference counterpart).  x = D^-1/2 X X^T
+// D^-1/2 is formed once as a full FP64 matrix padded to kTriTile (k_tri_gram); k_tri_scan walks the
+// tile triples I <= J <= K and evaluates the four inequalities of every i < j < k.  Which of the
+// qualifying ones (v > min_violation) are kept is decided by a radix select over the 128-bit key
+// (hi = ~bits(v): larger v first; lo = ((i n + j) n + k) 4 + type: lower index first) whose
+// counting passes are scans with integer atomics only, so every output is the same bits each run.
+// ------------------------------------------------------------------------
+static_assert(kTriTile == 32 && kBlock == 256, "k_tri_gram / k_tri_scan: 32 x 32 tiles, 4 pairs a thread");
+constexpr int kTriGramCols = 32;   // factor columns of one staged chunk of k_tri_gram
+
+// x[gi][gj] = <X_gi, X_gj> / (sb_gi sb_gj) over columns c < r in column order (fused multiply-adds,
+// whose products commute: x is bitwise symmetric); rows and columns n .. npad - 1 are zero.  One
+// block a 32 x 32 tile; the two row panels pass through LDS kTriGramCols columns at a time, padded
+// by one so that the 32 rows of a column fall on distinct banks.
+__global__ void __launch_bounds__(kBlock) k_tri_gram(int n, int r, int ld, int npad, const double *__restrict__ X,
+                                                     const double *__restrict__ sb, double *__restrict__ x) {
+    __shared__ double sA[kTriTile][kTriGramCols + 1], sB[kTriTile][kTriGramCols + 1];
+    const int j = threadIdx.x & 31, ib = threadIdx.x >> 5;
+    const int i0 = blockIdx.y * kTriTile, j0 = blockIdx.x * kTriTile;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c0 = 0; c0 < r; c0 += kTriGramCols) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = ib + 8 * q, c = c0 + j;   // a lane a column: 32 consecutive doubles of a row
+            sA[row][j] = (i0 + row < n && c < r) ? X[(long)(i0 + row) * ld + c] : 0.0;
+            sB[row][j] = (j0 + row < n && c < r) ? X[(long)(j0 + row) * ld + c] : 0.0;
+        }
+        __syncthreads();
+        const int nc = min(kTriGramCols, r - c0);
+        for (int c = 0; c < nc; ++c) {
+            const double b = sB[j][c];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = fma(sA[ib + 8 * q][c], b, acc[q]);
+        }
+    }
+    const int gj = j0 + j;
+    const double sj = gj < n ? sb[gj] : 1.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int gi = i0 + ib + 8 * q;
+        x[(long)gi * npad + gj] = (gi < n && gj < n) ? acc[q] / (sb[gi] * sj) : 0.0;
+    }
+}
+
+// One qualifying inequality (v > min_violation >= 0, so bits(v) orders as v does) in a scan of
+// mode MODE.  0, the first counting pass: the thread's count and largest v, the key's first digit.
+// 1, a later counting pass: the next digit of the keys under the prefix found so far.  2, the
+// collect pass: every key at or below the cut's prefix goes to rec through the integer cursor.
+template <int MODE>
+__device__ __forceinline__ void tri_hit(double v, unsigned long long idx, const TriPass &P, unsigned *hist,
+                                        unsigned &cnt, unsigned long long &vmax, unsigned *__restrict__ cursor,
+                                        ulonglong2 *__restrict__ rec) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(v), hi = ~bits;
+    if (MODE == 0) {
+        ++cnt;
+        vmax = bits > vmax ? bits : vmax;
+        atomicAdd(&hist[(unsigned)(hi >> P.shift) & P.mask], 1u);
+    } else if (MODE == 1) {
+        const bool in = P.part == 0 ? (hi >> P.pshift) == P.prefix : (hi == P.fixed_hi && (idx >> P.pshift) == P.prefix);
+        if (in) atomicAdd(&hist[(unsigned)((P.part == 0 ? hi : idx) >> P.shift) & P.mask], 1u);
+    } else {
+        const bool in = P.part == 0 ? (hi >> P.pshift) <= P.prefix
+                                    : (hi < P.fixed_hi || (hi == P.fixed_hi && (idx >> P.pshift) <= P.prefix));
+        if (in) {
+            const unsigned pos = atomicAdd(cursor, 1u);
+            if (pos < P.cap) rec[pos] = make_ulonglong2(bits, idx);   // the count past cap is the host's error
+        }
+    }
+}
+
+// Block (J, I, z), I <= J, takes the tile pair's 1024 (i, j): thread t holds x_ij of j = t & 31 and
+// i = (t >> 5) + 8 q, q = 0 .. 3, in registers and walks tiles K = J + z, J + z + S, ...  Per K the
+// tiles x[I][K] (row i: one address a half-wave) and x[K][J] (row k, lane j: consecutive; x is
+// symmetric, so this is x[J][K] transposed) are staged in LDS.  s = (+-x_ij +- x_ik) +- x_jk in
+// that order, v = -1 - s.  The guards i < j < k < n hold for every tile coincidence and for the
+// ragged last tile; the padded matrix makes every load in bounds.
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) k_tri_scan(int n, int npad, int S, double minv, TriPass P,
+                                                     const double *__restrict__ x,
+                                                     unsigned long long *__restrict__ ghist,
+                                                     unsigned long long *__restrict__ gcnt, unsigned *__restrict__ cursor,
+                                                     ulonglong2 *__restrict__ rec) {
+    const int I = blockIdx.y, J = blockIdx.x;
+    if (I > J) return;
+    __shared__ double sIK[kTriTile][kTriTile], sKJ[kTriTile][kTriTile];
+    __shared__ unsigned hist[MODE == 2 ? 1 : kTriBins];
+    __shared__ unsigned s_cnt;
+    __shared__ unsigned long long s_max;
+    const int t = threadIdx.x, j = t & 31, ib = t >> 5;
+    const int NT = npad / kTriTile;
+    if (MODE != 2)
+        for (int b = t; b < kTriBins; b += kBlock) hist[b] = 0u;
+    if (t == 0) { s_cnt = 0u; s_max = 0ull; }
+    const int gj = J * kTriTile + j;
+    double a[4];
+    bool okij[4];
+    unsigned long long base[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int gi = I * kTriTile + ib + 8 * q;
+        a[q] = x[(long)gi * npad + gj];
+        okij[q] = gi < gj;
+        base[q] = ((unsigned long long)gi * (unsigned)n + (unsigned)gj) * (unsigned)n;
+    }
+    unsigned cnt = 0u;
+    unsigned long long vmax = 0ull;
+    for (int K = J + (int)blockIdx.z; K < NT; K += S) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = ib + 8 * q;
+            sIK[row][j] = x[(long)(I * kTriTile + row) * npad + K * kTriTile + j];
+            sKJ[row][j] = x[(long)(K * kTriTile + row) * npad + J * kTriTile + j];
+        }
+        __syncthreads();
+        const int k0 = K * kTriTile;
+        for (int k = 0; k < kTriTile; ++k) {
+            const int gk = k0 + k;
+            if (gk >= n) break;
+            const bool okk = gj < gk;
+            const double c = sKJ[k][j];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const double b = sIK[ib + 8 * q][k];
+                const double ab = a[q] + b, amb = a[q] - b;
+                const double v0 = -1.0 - (ab + c), v1 = -1.0 - (amb - c), v2 = -1.0 - (-amb - c), v3 = -1.0 - (c - ab);
+                const bool any = (v0 > minv) | (v1 > minv) | (v2 > minv) | (v3 > minv);
+                if (any && okk && okij[q]) {
+                    const unsigned long long idx = (base[q] + (unsigned)gk) * 4ull;
+                    if (v0 > minv) tri_hit<MODE>(v0, idx, P, hist, cnt, vmax, cursor, rec);
+                    if (v1 > minv) tri_hit<MODE>(v1, idx + 1, P, hist, cnt, vmax, cursor, rec);
+                    if (v2 > minv) tri_hit<MODE>(v2, idx + 2, P, hist, cnt, vmax, cursor, rec);
+                    if (v3 > minv) tri_hit<MODE>(v3, idx + 3, P, hist, cnt, vmax, cursor, rec);
+                }
+            }
+        }
+    }
+    if (MODE == 2) return;
+    if (MODE == 0 && cnt) {
+        atomicAdd(&s_cnt, cnt);
+        atomicMax(&s_max, vmax);
+    }
+    __syncthreads();
+    for (int b = t; b < kTriBins; b += kBlock)
+        if (const unsigned h = hist[b]) atomicAdd(&ghist[b], (unsigned long long)h);
+    if (MODE == 0 && t == 0 && s_cnt) {
+        atomicAdd(&gcnt[0], (unsigned long long)s_cnt);
+        atomicMax(&gcnt[1], s_max);
+    }
+}
+
+int tri_pad(int n) { return (n + kTriTile - 1) / kTriTile * kTriTile; }
+
+int launch_tri_gram(const DevCone &c, const double *X, const double *sb, double *x, hipStream_t st) {
+    const int npad = tri_pad(c.n), NT = npad / kTriTile;
+    hipLaunchKernelGGL(k_tri_gram, dim3(NT, NT), dim3(kBlock), 0, st, c.n, c.r, c.ld, npad, X, sb, x);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_tri_scan(int mode, int n, double minv, const TriPass &P, const double *x, unsigned long long *ghist,
+                    unsigned long long *gcnt, unsigned *cursor, void *rec, hipStream_t st) {
+    const int npad = tri_pad(n), NT = npad / kTriTile;
+    // enough blocks to fill the device when there are few tile pairs: the K tiles of a pair dealt to S blocks
+    const long pairs = (long)NT * (NT + 1) / 2;
+    const int S = (int)std::min<long>(NT, std::max<long>(1, (4096 + pairs - 1) / pairs));
+    const dim3 grid(NT, NT, S);
+    ulonglong2 *r2 = (ulonglong2 *)rec;
+    if (mode == 0) hipLaunchKernelGGL(k_tri_scan<0>, grid, dim3(kBlock), 0, st, n, npad, S, minv, P, x, ghist, gcnt, cursor, r2);
+    else if (mode == 1) hipLaunchKernelGGL(k_tri_scan<1>, grid, dim3(kBlock), 0, st, n, npad, S, minv, P, x, ghist, gcnt, cursor, r2);
+    else hipLaunchKernelGGL(k_tri_scan<2>, grid, dim3(kBlock), 0, st, n, npad, S, minv, P, x, ghist, gcnt, cursor, r2);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace lrs

@@ -178,6 +178,10 @@ struct lrs_ctx {
     // counts; allocated on first use, grown when a call needs more, freed with the context
     void *round_buf = nullptr;
     size_t round_bytes = 0;
+    // triangle separation (lrs_separate_triangles): the normalised Gram matrix,
+    // sqrt(b), the histogram, the counters and the collected records; same life cycle
+    void *tri_buf = nullptr;
+    size_t tri_bytes = 0;
     double *d_sendvec = nullptr;   // sharded: packed send rows of one Lanczos vector
     long sendvec_len = 0;
     // initial point cache (device layout, host copy) for the ranks it was drawn at
@@ -3045,7 +3049,7 @@ void lrs_ctx_destroy(lrs_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     delete c->comm;
     for (void *q : {(void *)c->s_tickets, (void *)c->s_tmpfin, (void *)c->s_rpart, (void *)c->s_fin, (void *)c->d_sendbuf,
-                    (void *)c->d_sendvec, (void *)c->Cw0, (void *)c->Craw0, (void *)c->xwg_snap, c->round_buf})
+                    (void *)c->d_sendvec, (void *)c->Cw0, (void *)c->Craw0, (void *)c->xwg_snap, c->round_buf, c->tri_buf})
         if (q) (void)hipFree(q);
     for (int *q : c->d_send_rows)
         if (q) (void)hipFree(q);
@@ -3566,21 +3570,21 @@ int lrs_round_dirs(unsigned long long seed, int r, int trials, double *out) {
 // Whether cone k is a diagonally constrained cone of its own: n consecutive constraints o .. o +
 // n - 1, constraint o + i being the single entry (i, i) of this cone and touching no other cone,
 // and no other constraint in the cone.  sb[i] = sqrt(b_i / a_i) (a_i the entry's coefficient, 1 in
-// MaxCut).  Returns 0, or the refusal's code with the message set.
-static int round_qualify(lrs_ctx *c, int k, std::vector<double> &sb) {
+// MaxCut).  Returns 0, or the refusal's code with the message set (`who` names the caller in it).
+static int round_qualify(lrs_ctx *c, int k, std::vector<double> &sb, const char *who = "lrs_round_signs") {
     const HostCone &hc = c->hp.cones[k];
     const int n = hc.n;
     if ((int)hc.ent.size() != n || n < 1) {
-        set_err("lrs_round_signs: cone %d is not diagonally constrained (%zu constraint entries on %d rows; "
-                "X_ii = b_i for every i and nothing else is required)", k, hc.ent.size(), n);
+        set_err("%s: cone %d is not diagonally constrained (%zu constraint entries on %d rows; "
+                "X_ii = b_i for every i and nothing else is required)", who, k, hc.ent.size(), n);
         return -7;
     }
     const int o = hc.ent[0].con;
     for (int i = 0; i < n; ++i) {
         const HostEntry &e = hc.ent[i];
         if (e.con != o + i || hc.prow[e.slot] != i || hc.pcol[e.slot] != i) {
-            set_err("lrs_round_signs: cone %d is not diagonally constrained (constraint %d is not the single entry "
-                    "(%d, %d))", k, e.con + 1, i + 1, i + 1);
+            set_err("%s: cone %d is not diagonally constrained (constraint %d is not the single entry "
+                    "(%d, %d))", who, k, e.con + 1, i + 1, i + 1);
             return -7;
         }
     }
@@ -3593,8 +3597,8 @@ static int round_qualify(lrs_ctx *c, int k, std::vector<double> &sb) {
         for (int con : oc.dense_con) shared = shared || hit(con);
         for (int con : oc.r_con) shared = shared || hit(con);
         if (shared) {
-            set_err("lrs_round_signs: cone %d is not diagonally constrained on its own (cone %d has entries in its "
-                    "constraints, so rounding the cone alone is not feasible)", k, k2);
+            set_err("%s: cone %d is not diagonally constrained on its own (cone %d has entries in its "
+                    "constraints, so rounding the cone alone is not feasible)", who, k, k2);
             return -7;
         }
     }
@@ -3602,7 +3606,7 @@ static int round_qualify(lrs_ctx *c, int k, std::vector<double> &sb) {
     for (int i = 0; i < n; ++i) {
         const double v = c->hp.b[o + i] / hc.ent[i].a;
         if (!(v > 0.0)) {
-            set_err("lrs_round_signs: cone %d, row %d: b_i = %g on coefficient %g (every X_ii must be > 0)", k, i + 1,
+            set_err("%s: cone %d, row %d: b_i = %g on coefficient %g (every X_ii must be > 0)", who, k, i + 1,
                     c->hp.b[o + i], hc.ent[i].a);
             return -8;
         }
@@ -3693,6 +3697,158 @@ int lrs_round_signs(lrs_ctx *c, int cone, int which, int trials, const double *d
     if (best_trial) *best_trial = bt;
     if (best_value) *best_value = hv[bt];
     if (sweeps) *sweeps = sw;
+    return 0;
+}
+
+// ---- triangle-inequality separation (no reference counterpart)
+// The radix digits of the 128-bit key, most significant first: the 64 bits of hi = ~bits(v), then
+// the 48 low bits of lo (the index is below 4 n^3 <= 2^47 at n <= LRS_TRI_MAX_N).
+static const struct { int part, shift, width; } kTriDigits[] = {
+    {0, 52, 12}, {0, 40, 12}, {0, 28, 12}, {0, 16, 12}, {0, 4, 12}, {0, 0, 4},
+    {1, 36, 12}, {1, 24, 12}, {1, 12, 12}, {1, 0, 12}};
+
+int lrs_separate_triangles(lrs_ctx *c, int cone, int which, int max_cuts, double min_violation, int *cuts,
+                           double *violation, int *n_cuts, long long *n_violated, double *max_violation) {
+    LRS_NEED_LOADED(c);
+    if (max_cuts < 1 || max_cuts > LRS_TRI_MAX_K) {
+        set_err("lrs_separate_triangles: max_cuts = %d (1 .. %d)", max_cuts, LRS_TRI_MAX_K);
+        return -2;
+    }
+    if (!(min_violation >= 0.0)) {
+        set_err("lrs_separate_triangles: min_violation = %g (>= 0)", min_violation);
+        return -12;
+    }
+    if (sharded(c)) { set_err("lrs_separate_triangles: sharded contexts are not supported"); return -3; }
+    if (cone < 0 || cone >= c->dp.K) { set_err("lrs_separate_triangles: cone %d of %d", cone, c->dp.K); return -4; }
+    if (is_lp(c, cone)) { set_err("lrs_separate_triangles: cone %d is the LP block", cone); return -5; }
+    if (!c->walloc) { set_err("lrs_separate_triangles: no solver state (ranks not set)"); return -6; }
+    if (which < LRS_R || which > LRS_V) { set_err("lrs_separate_triangles: factor %d (LRS_R .. LRS_V)", which); return -11; }
+    const DevCone &dc = c->dp.cones[cone];
+    if (dc.kd || dc.rp) {
+        set_err("lrs_separate_triangles: cone %d has dense or rank-one constraint matrices", cone);
+        return -10;
+    }
+    std::vector<double> sb;
+    if (int rc = round_qualify(c, cone, sb, "lrs_separate_triangles")) return rc;
+    const int n = dc.n;
+    if (n < 3) { set_err("lrs_separate_triangles: cone %d has %d rows (a triangle needs 3)", cone, n); return -13; }
+    if (n > LRS_TRI_MAX_N) {
+        set_err("lrs_separate_triangles: cone %d has %d rows; the %d x %d matrix of x_ij is kept on the device and "
+                "capped at 8 GiB (n <= %d)", cone, n, n, n, LRS_TRI_MAX_N);
+        return -14;
+    }
+    // the records the collect pass may append: enough to cover the cut's last bucket, small enough
+    // that a large tie is split on the index digits instead
+    const unsigned cap = (unsigned)std::min<long>(4L * LRS_TRI_MAX_K, std::max<long>(4096, 16L * max_cuts));
+    const size_t npad = (size_t)tri_pad(n);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_x = 0, o_sb = o_x + al(sizeof(double) * npad * npad), o_hist = o_sb + al(sizeof(double) * n),
+                 o_cnt = o_hist + al(sizeof(unsigned long long) * kTriBins), o_rec = o_cnt + al(32),
+                 total = o_rec + al(16 * (size_t)cap);
+    if (total > c->tri_bytes) {
+        HIPC(hipStreamSynchronize(c->st));
+        if (c->tri_buf) (void)hipFree(c->tri_buf);
+        c->tri_buf = nullptr;
+        c->tri_bytes = 0;
+        HIPC(hipMalloc(&c->tri_buf, total));
+        c->tri_bytes = total;
+    }
+    char *base = (char *)c->tri_buf;
+    double *d_x = (double *)(base + o_x), *d_sb = (double *)(base + o_sb);
+    unsigned long long *d_hist = (unsigned long long *)(base + o_hist), *d_cnt = (unsigned long long *)(base + o_cnt);
+    unsigned *d_cur = (unsigned *)(base + o_cnt + 16);
+    void *d_rec = base + o_rec;
+    HIPC(h2d_sync(c, d_sb, sb.data(), sizeof(double) * n));
+    OPC(launch_tri_gram(dc, factor_ptr(c, which) + dc.foff, d_sb, d_x, c->st));
+    // a scan: the histogram, the counters and the cursor zeroed, the pass, what the host reads back
+    std::vector<unsigned long long> hist(kTriBins);
+    unsigned long long hcnt[4] = {0, 0, 0, 0};
+    auto scan = [&](int mode, const TriPass &P) -> int {
+        HIPC(hipMemsetAsync(d_hist, 0, o_rec - o_hist, c->st));
+        OPC(launch_tri_scan(mode, n, min_violation, P, d_x, d_hist, d_cnt, d_cur, d_rec, c->st));
+        if (mode != 2) HIPC(hipMemcpyAsync(hist.data(), d_hist, sizeof(unsigned long long) * kTriBins, hipMemcpyDeviceToHost, c->st));
+        HIPC(hipMemcpyAsync(hcnt, d_cnt, sizeof(hcnt), hipMemcpyDeviceToHost, c->st));
+        HIPC(hipStreamSynchronize(c->st));
+        return 0;
+    };
+    TriPass P{};
+    P.cap = cap;
+    P.part = 0;
+    P.shift = kTriDigits[0].shift;
+    P.mask = (1u << kTriDigits[0].width) - 1u;
+    if (scan(0, P)) return -1;
+    const unsigned long long total_v = hcnt[0];
+    double vmax = 0.0;
+    memcpy(&vmax, &hcnt[1], sizeof(double));
+    if (n_violated) *n_violated = (long long)total_v;
+    if (max_violation) *max_violation = total_v ? vmax : 0.0;
+    if (n_cuts) *n_cuts = 0;
+    if (!total_v) return 0;
+    const unsigned long long K = std::min<unsigned long long>((unsigned long long)max_cuts, total_v);
+    // narrow the cut's prefix digit by digit: `below` keys sort before the prefix's bucket (all of
+    // them kept, below < K), the bucket holds the K-th; stop when both fit the records
+    unsigned long long below = 0, bucket = total_v, expect = total_v;
+    P.pshift = 63;
+    P.prefix = 1;   // (hi >> 63) <= 1: every key
+    for (size_t d = 0; below + bucket > cap; ++d) {
+        if (d >= sizeof(kTriDigits) / sizeof(kTriDigits[0])) {
+            set_err("lrs_separate_triangles: the selection did not end (internal error)");
+            return -1;
+        }
+        const auto &dg = kTriDigits[d];
+        if (d > 0) {   // the first digit's histogram came with the first pass
+            if (dg.part == 1 && kTriDigits[d - 1].part == 0) {   // hi is fixed: on to the index
+                P.fixed_hi = P.prefix;
+                P.prefix = 0;
+                P.pshift = 48;
+            }
+            P.part = dg.part;
+            P.shift = dg.shift;
+            P.mask = (1u << dg.width) - 1u;
+            if (scan(1, P)) return -1;
+        } else {
+            P.prefix = 0;
+        }
+        unsigned b = 0;
+        unsigned long long cum = below;
+        for (; b < (1u << dg.width) && cum + hist[b] < K; ++b) cum += hist[b];
+        if (b >= (1u << dg.width)) {
+            set_err("lrs_separate_triangles: a counting pass lost keys (internal error)");
+            return -1;
+        }
+        below = cum;
+        bucket = hist[b];
+        P.prefix = (P.prefix << dg.width) | b;
+        P.pshift = dg.shift;
+        P.part = dg.part;
+        expect = below + bucket;
+    }
+    if (scan(2, P)) return -1;
+    unsigned cur = 0;
+    memcpy(&cur, (char *)hcnt + 16, sizeof(unsigned));
+    if (cur != expect || cur > cap) {
+        set_err("lrs_separate_triangles: %u records collected, %llu expected (internal error)", cur, expect);
+        return -1;
+    }
+    std::vector<unsigned long long> rec(2 * (size_t)cur);
+    HIPC(hipMemcpy(rec.data(), d_rec, 16 * (size_t)cur, hipMemcpyDeviceToHost));
+    std::vector<unsigned> ord(cur);
+    for (unsigned q = 0; q < cur; ++q) ord[q] = q;
+    // the total order: v descending (bits of a positive double order as the double), index ascending
+    std::sort(ord.begin(), ord.end(), [&](unsigned p, unsigned q) {
+        return rec[2 * p] != rec[2 * q] ? rec[2 * p] > rec[2 * q] : rec[2 * p + 1] < rec[2 * q + 1];
+    });
+    for (unsigned long long t = 0; t < K; ++t) {
+        const unsigned long long bits = rec[2 * ord[t]], idx = rec[2 * ord[t] + 1], ijk = idx >> 2;
+        if (cuts) {
+            cuts[4 * t] = (int)(ijk / ((unsigned long long)n * n));
+            cuts[4 * t + 1] = (int)(ijk / n % n);
+            cuts[4 * t + 2] = (int)(ijk % n);
+            cuts[4 * t + 3] = (int)(idx & 3);
+        }
+        if (violation) memcpy(&violation[t], &bits, sizeof(double));
+    }
+    if (n_cuts) *n_cuts = (int)K;
     return 0;
 }
 

@@ -14,6 +14,11 @@
 // (default 0), `--roundLocalSearch 0|1` (default 1), `--roundFile PATH` (the best assignment, one
 // +1 / -1 a line in cone order); the JSON gains a "rounding" object.  A problem that does not
 // qualify keeps its output as it is, with one line on stderr.
+// `--triangleCuts K` (default 0 = off) then finds the K most violated triangle inequalities of
+// every diagonally constrained cone's R (lrs_separate_triangles) with violation
+// above `--triangleMinViol v` (default 0); `--triangleFile PATH` receives them, `i j k type
+// violation` a line (i < j < k 1-based, type 0..3, %.17g); the JSON gains a "triangles" object.  A
+// cone that does not qualify gets one line on stderr and nothing else.
 #include <getopt.h>
 
 #include <cctype>
@@ -69,6 +74,9 @@ struct Flags {
     int roundTrials = 0, roundLocalSearch = 1;
     unsigned long long roundSeed = 0;
     std::string roundFile;
+    int triangleCuts = 0;
+    double triangleMinViol = 0.0;
+    std::string triangleFile;
 };
 static void parse_flags(int argc, char **argv, Flags &F) {
     lrs_params &p = F.p;
@@ -91,7 +99,9 @@ static void parse_flags(int argc, char **argv, Flags &F) {
         {"disableOracle", no_argument, 0, 2002}, {"device", required_argument, 0, 2003},
         {"quiet", no_argument, 0, 2004}, {"batch", required_argument, 0, 2005},
         {"roundTrials", required_argument, 0, 2006}, {"roundSeed", required_argument, 0, 2007},
-        {"roundLocalSearch", required_argument, 0, 2008}, {"roundFile", required_argument, 0, 2009}, {0, 0, 0, 0}};
+        {"roundLocalSearch", required_argument, 0, 2008}, {"roundFile", required_argument, 0, 2009},
+        {"triangleCuts", required_argument, 0, 2010}, {"triangleMinViol", required_argument, 0, 2011},
+        {"triangleFile", required_argument, 0, 2012}, {0, 0, 0, 0}};
     int opt, li = 0;
     optind = 0;   // a fresh scan (one per manifest line)
     while ((opt = getopt_long(argc, argv, "r:", opts, &li)) != -1) {
@@ -133,6 +143,9 @@ static void parse_flags(int argc, char **argv, Flags &F) {
         case 2007: F.roundSeed = strtoull(optarg, nullptr, 10); break;
         case 2008: F.roundLocalSearch = atoi(optarg); break;
         case 2009: F.roundFile = optarg; break;
+        case 2010: F.triangleCuts = atoi(optarg); break;
+        case 2011: F.triangleMinViol = atof(optarg); break;
+        case 2012: F.triangleFile = optarg; break;
         default: break;   // unknown flags: getopt already printed a message; ignored like main.c
         }
     }
@@ -152,6 +165,27 @@ static void finish_flags(Flags &F, std::vector<int> &sched) {
         fprintf(stderr, "[lrsdp] lbfgsListLength %d < 1; using 2\n", p.lbfgsListLength);
         p.lbfgsListLength = 2;
     }
+}
+
+// lrs_write_json's text ends with the top-level closing brace: `obj` (from its leading comma to the
+// new closing brace) takes the place of that brace and the white space before it
+static void json_append(const char *jsonFile, const std::string &obj) {
+    FILE *f = fopen(jsonFile, "rb");
+    if (!f) return;
+    std::string s;
+    char buf[4096];
+    size_t nr;
+    while ((nr = fread(buf, 1, sizeof(buf), f)) > 0) s.append(buf, nr);
+    fclose(f);
+    const size_t close = s.find_last_of('}');
+    if (close == std::string::npos) return;
+    size_t end = close;
+    while (end > 0 && isspace((unsigned char)s[end - 1])) end--;
+    s = s.substr(0, end) + obj;
+    f = fopen(jsonFile, "wb");
+    if (!f) return;
+    fwrite(s.data(), 1, s.size(), f);
+    fclose(f);
 }
 
 // --roundTrials T after a solve: every cone's R rounded on the context's own stream (per cone the
@@ -201,28 +235,86 @@ static void round_and_report(lrs_ctx *ctx, const Flags &F, const char *jsonFile)
         }
     }
     if (!jsonFile) return;
-    // lrs_write_json's text ends with the top-level closing brace: the object goes in before it
-    FILE *f = fopen(jsonFile, "rb");
-    if (!f) return;
-    std::string s;
-    char buf[4096];
-    size_t nr;
-    while ((nr = fread(buf, 1, sizeof(buf), f)) > 0) s.append(buf, nr);
-    fclose(f);
-    const size_t close = s.find_last_of('}');
-    if (close == std::string::npos) return;
-    size_t end = close;
-    while (end > 0 && isspace((unsigned char)s[end - 1])) end--;
     char obj[512];
     snprintf(obj, sizeof(obj),
              ",\n  \"rounding\": {\n    \"trials\": %d,\n    \"seed\": %llu,\n    \"local_search\": %d,\n"
              "    \"value\": %.16e,\n    \"best_trial\": %s,\n    \"sweeps\": %d,\n    \"time_sec\": %.16e\n  }\n}\n",
              F.roundTrials, F.roundSeed, F.roundLocalSearch ? 1 : 0, value, bt.c_str(), sweeps, secs);
-    s = s.substr(0, end) + obj;
-    f = fopen(jsonFile, "wb");
-    if (!f) return;
-    fwrite(s.data(), 1, s.size(), f);
-    fclose(f);
+    json_append(jsonFile, obj);
+}
+
+// --triangleCuts K after a solve (and after the rounding): every cone's R separated on the
+// context's own stream.  The cones that qualify are reported in cone order: the JSON at jsonFile
+// (if any) gains "triangles" (n_cuts, n_violated, max_violation, time_sec: numbers with one such
+// cone, lists with several) and triangleFile receives their cuts ("# cone k" before each cone's
+// lines when there are several).  A cone that does not qualify costs one stderr line.
+static void triangles_and_report(lrs_ctx *ctx, const Flags &F, const char *jsonFile) {
+    if (F.triangleCuts <= 0) return;
+    int K = 0;
+    lrs_problem_info(ctx, nullptr, &K, nullptr, nullptr, nullptr);
+    const int cap = F.triangleCuts < LRS_TRI_MAX_K ? F.triangleCuts : LRS_TRI_MAX_K;
+    struct Cone {
+        int k, n_cuts;
+        long long n_violated;
+        double max_violation, secs;
+        std::vector<int> cuts;
+        std::vector<double> viol;
+    };
+    std::vector<Cone> done;
+    for (int k = 0; k < K; ++k) {
+        Cone c;
+        c.k = k;
+        c.cuts.resize(4 * (size_t)cap);
+        c.viol.resize(cap);
+        lrs_sync(ctx);
+        timespec t0, t1;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        const int rc = lrs_separate_triangles(ctx, k, LRS_R, F.triangleCuts, F.triangleMinViol, c.cuts.data(), c.viol.data(),
+                                              &c.n_cuts, &c.n_violated, &c.max_violation);
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        if (rc) {
+            fprintf(stderr, "[lrsdp] triangles skipped: %s\n", lrs_last_error());
+            continue;
+        }
+        c.secs = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+        printf("Triangles: cone %d: %lld violated by more than %g (largest %.10e), %d returned (%f s)\n", k, c.n_violated,
+               F.triangleMinViol, c.max_violation, c.n_cuts, c.secs);
+        done.push_back(std::move(c));
+    }
+    if (done.empty()) return;
+    if (!F.triangleFile.empty()) {
+        FILE *f = fopen(F.triangleFile.c_str(), "w");
+        if (!f) fprintf(stderr, "[lrsdp] cannot open %s\n", F.triangleFile.c_str());
+        else {
+            for (const Cone &c : done) {
+                if (done.size() > 1) fprintf(f, "# cone %d\n", c.k + 1);
+                for (int t = 0; t < c.n_cuts; ++t)
+                    fprintf(f, "%d %d %d %d %.17g\n", c.cuts[4 * t] + 1, c.cuts[4 * t + 1] + 1, c.cuts[4 * t + 2] + 1,
+                            c.cuts[4 * t + 3], c.viol[t]);
+            }
+            fclose(f);
+        }
+    }
+    if (!jsonFile) return;
+    auto list = [&](auto field) {
+        std::string s = done.size() == 1 ? "" : "[";
+        for (size_t q = 0; q < done.size(); ++q) s += (q ? ", " : "") + field(done[q]);
+        return done.size() == 1 ? s : s + "]";
+    };
+    auto num = [](double v) {
+        char b[40];
+        snprintf(b, sizeof(b), "%.16e", v);
+        return std::string(b);
+    };
+    char head[160];
+    snprintf(head, sizeof(head), ",\n  \"triangles\": {\n    \"max_cuts\": %d,\n    \"min_violation\": %.16e,\n",
+             F.triangleCuts, F.triangleMinViol);
+    const std::string obj = std::string(head) +
+        "    \"n_cuts\": " + list([](const Cone &c) { return std::to_string(c.n_cuts); }) + ",\n" +
+        "    \"n_violated\": " + list([](const Cone &c) { return std::to_string(c.n_violated); }) + ",\n" +
+        "    \"max_violation\": " + list([&](const Cone &c) { return num(c.max_violation); }) + ",\n" +
+        "    \"time_sec\": " + list([&](const Cone &c) { return num(c.secs); }) + "\n  }\n}\n";
+    json_append(jsonFile, obj);
 }
 
 // --batch FILE: load every line's instance, one lrs_solve_batch, one JSON each
@@ -331,6 +423,7 @@ static int run_batch(const Flags &base, const char *prog) {
             printf("%s: pObj %10.6e dObj %10.6e ALM inner %ld ADMM %ld all_time %f -> %s\n", pid.c_str(), res[q].pobj,
                    res[q].dobj, res[q].alm_inner, res[q].admm_iter, res[q].solve_time, j->F.jsonFile.c_str());
             round_and_report(j->ctx, j->F, j->F.jsonFile.c_str());   // each member on its own stream
+            triangles_and_report(j->ctx, j->F, j->F.jsonFile.c_str());
         }
         long launches = 0, served = 0, alone = 0;
         int widest = 0;
@@ -422,6 +515,7 @@ int main(int argc, char **argv) {
             printf("JSON output written to: %s\n", jsonFile);
     }
     round_and_report(ctx, F, jsonFile);
+    triangles_and_report(ctx, F, jsonFile);
     lrs_ctx_destroy(ctx);
     return 0;
 }

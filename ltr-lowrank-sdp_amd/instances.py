@@ -35,6 +35,7 @@ __all__ = [
     "write_sdpa",
     "config_instance",
     "maxcut_lp",
+    "add_triangle_cuts",
     "dense_constraints_problem",
     "dense_constraints",
     "rank_one_constraints_problem",
@@ -264,6 +265,52 @@ def maxcut_lp(path, n, p_edge, seed):
     ents.append((np.array([m, m]), 2, np.array([n + 1, n + 2]), np.array([n + 1, n + 2]), np.array([1.0, -1.0])))
     b = np.concatenate([np.ones(n), [0.0]])
     return write_sdpa(path, m, [n, -nlp], b, ents)
+
+
+# sign of x_ij, x_ik, x_jk in the triangle inequality of each type (include/lrsdp.h lrs_separate_triangles)
+TRIANGLE_SIGNS = np.array([[1.0, 1.0, 1.0], [1.0, -1.0, -1.0], [-1.0, 1.0, -1.0], [-1.0, -1.0, 1.0]])
+
+
+def add_triangle_cuts(problem, cuts, b=None):
+    """A MaxCut-class problem (m, dims, b, entries) with one SDP block plus the triangle
+    inequalities `cuts` (rows {i, j, k, type}, 0-based, i < j < k, as Solver.separate_triangles
+    returns them): a new problem in the same form for write_sdpa / coo_arrays.  Cut t becomes
+    constraint m + 1 + t: sigma_ij x_ij + sigma_ik x_ik + sigma_jk x_jk - s_t = -1 with x_ij = X_ij
+    / sqrt(b_i b_j) and the slack s_t >= 0 column t of one LP block appended last (size -T), so
+    each pair gets the SDPA entry (row < col) sigma / (2 sqrt(b_i b_j)): a symmetric off-diagonal
+    entry counts twice in <A, X>.  b: the diagonal X_ii by row (default: the problem's b, which
+    is X_ii when constraint i is X_ii = b_i as _maxcut_problem writes it)."""
+    m, dims, rhs, entries = problem
+    dims = [int(d) for d in dims]
+    if any(d < 0 for d in dims):
+        raise ValueError("add_triangle_cuts: the problem already has an LP block")
+    if len(dims) != 1:
+        raise ValueError(f"add_triangle_cuts: {len(dims)} SDP blocks (exactly one is supported)")
+    n = dims[0]
+    cuts = np.asarray(cuts, dtype=np.int64).reshape(-1, 4)
+    T = cuts.shape[0]
+    if T == 0:
+        raise ValueError("add_triangle_cuts: no cuts")
+    i, j, k, ty = cuts.T
+    if not ((0 <= i) & (i < j) & (j < k) & (k < n) & (0 <= ty) & (ty < 4)).all():
+        raise ValueError("add_triangle_cuts: a cut is not {i < j < k < n, type 0..3}")
+    rhs = np.asarray(rhs, dtype=np.float64)
+    if b is None:
+        if rhs.size < n:
+            raise ValueError("add_triangle_cuts: b is needed (the problem has fewer constraints than rows)")
+        b = rhs[:n]
+    b = np.asarray(b, dtype=np.float64)
+    if b.shape != (n,) or not (b > 0).all():
+        raise ValueError("add_triangle_cuts: b must hold n positive values")
+    sig = TRIANGLE_SIGNS[ty]                                   # (T, 3): pairs (i, j), (i, k), (j, k)
+    lo = np.stack([i, i, j], axis=1)
+    hi = np.stack([j, k, k], axis=1)
+    val = sig / (2.0 * np.sqrt(b[lo] * b[hi]))
+    con = np.repeat(np.arange(m + 1, m + 1 + T), 3)
+    slack = np.arange(1, T + 1)
+    new = [(con, 1, lo.ravel() + 1, hi.ravel() + 1, val.ravel()),
+           (np.arange(m + 1, m + 1 + T), 2, slack, slack, -np.ones(T))]
+    return m + T, dims + [-T], np.concatenate([rhs, -np.ones(T)]), list(entries) + new
 
 
 def dense_constraints_problem(dims, m_sparse, k, fills, cross, seed):

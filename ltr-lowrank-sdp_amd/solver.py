@@ -168,6 +168,8 @@ def load_library(path=None):
         "lrs_round_dirs": (C.c_int, [C.c_ulonglong, C.c_int, C.c_int, dp]),
         "lrs_round_signs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, C.c_ulonglong, C.c_int, C.c_int, dp,
                                       C.POINTER(C.c_ulonglong), ip, dp, C.POINTER(C.c_byte), ip]),
+        "lrs_separate_triangles": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, ip, dp, ip,
+                                             C.POINTER(C.c_longlong), dp]),
         "lrs_shard_plan": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_long), ip, ip, ip, ip, ip, ip, ip]),
     }
     for name, (res, args) in sig.items():
@@ -218,6 +220,15 @@ class RoundError(RuntimeError):
 
     def __init__(self, code, msg):
         super().__init__(f"round_signs ({code}): {msg}")
+        self.code = code
+        self.message = msg
+
+
+class TriangleError(RuntimeError):
+    """A refused Solver.separate_triangles: `code` is lrs_separate_triangles' negative return value."""
+
+    def __init__(self, code, msg):
+        super().__init__(f"separate_triangles ({code}): {msg}")
         self.code = code
         self.message = msg
 
@@ -520,6 +531,26 @@ class Solver:
             raise RoundError(rc, self.lib.lrs_last_error().decode())
         return {"values": values[:trials], "bits": bits, "best_trial": bt.value, "best_value": bv.value, "x": x[:n],
                 "sweeps": sw.value}
+
+    # ---- triangle-inequality separation (include/lrsdp.h lrs_separate_triangles)
+    def separate_triangles(self, max_cuts, min_violation=0.0, cone=0, which=R):
+        """The `max_cuts` most violated triangle inequalities of factor `which` of a diagonally
+        constrained cone, found on the device: (cuts (n_cuts, 4) int32 rows {i, j, k, type},
+        0-based with i < j < k; violation (n_cuts,), descending, ties by (i, j, k, type);
+        n_violated, the exact number with violation > min_violation; max_violation).
+        instances.add_triangle_cuts turns the cuts into constraints.  A refusal raises
+        TriangleError with the library's negative code."""
+        max_cuts = int(max_cuts)
+        cap = max(1, min(max_cuts, 65536))
+        cuts = np.zeros((cap, 4), dtype=np.int32)
+        viol = np.zeros(cap)
+        nc, nv, mv = C.c_int(), C.c_longlong(), C.c_double()
+        rc = self.lib.lrs_separate_triangles(self.ctx, cone, which, max_cuts, float(min_violation),
+                                             cuts.ctypes.data_as(C.POINTER(C.c_int)), _dptr(viol), C.byref(nc),
+                                             C.byref(nv), C.byref(mv))
+        if rc != 0:
+            raise TriangleError(rc, self.lib.lrs_last_error().decode())
+        return cuts[:nc.value].copy(), viol[:nc.value].copy(), nv.value, mv.value
 
     # ---- solves
     def solve(self, **kw):
