@@ -25,8 +25,9 @@
 #define LRSDP_H
 /* ABI revision, also in lrs_version()'s string.  2: lrs_op_admm_half takes (cone, side) and
  * refreshes the cone's constraint values itself (was: the whole sweep's first half-step);
- * lrs_op_alm_update, lrs_op_adjoint, lrs_op_auv and lrs_op_dimacs added. */
-#define LRSDP_ABI_VERSION 2
+ * lrs_op_alm_update, lrs_op_adjoint, lrs_op_auv and lrs_op_dimacs added.
+ * 3: lrs_solve_warm, lrs_cuts_append / _drop / _get / _state and lrs_certified_bound added. */
+#define LRSDP_ABI_VERSION 3
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -318,6 +319,71 @@ int lrs_separate_triangles(lrs_ctx *ctx, int cone, int which, int max_cuts, doub
                            int *cuts /* [max_cuts][4]: i, j, k (0-based, i<j<k), type 0..3 */,
                            double *violation /* [max_cuts] */, int *n_cuts,
                            long long *n_violated, double *max_violation);
+/* ---- Cutting-plane rounds in one context.  No reference counterpart.
+ * lrs_solve_warm: lrs_solve's flow (ALM phase, ALM-to-ADMM, ADMM, reopt rounds, dual infeasibility,
+ * trajectories, JSON state) with the ALM phase started from the context's current R (what
+ * lrs_factor_get(LRS_R) returns) and LAMBDA (lrs_vec_get(LRS_LAMBDA)) at its current ranks.
+ * Everything else is a cold start's: D, G, the L-BFGS pairs, the control block, U, V and the CG
+ * work are reset, rho comes from the parameters, rank_max is lrs_determine_rank's for the current
+ * m, and the current ranks are kept, clipped to it (a clipped cone keeps its leading columns);
+ * AUG_RANK may grow them.  The start is evaluated first, and one that already meets the phase-1
+ * test leaves the ALM phase at once, with alm_inner = 0.  If the previous solve's reopt rounds left
+ * obj_scale != 1, LAMBDA is first divided by it: the multipliers are brought back to the unscaled
+ * objective's units, as the objective itself is.  Refusals: -3 a sharded context, -6 ranks not set
+ * (no workspace), -1 lbfgsListLength < 1 and the header's general failures.
+ * Registered triangle cuts.  A context whose problem is one SDP cone diagonally constrained in
+ * lrs_round_signs' sense by constraints 1 .. n (m = n), with no LP block of its own, keeps a list
+ * of triangle inequalities {i, j, k, type} (lrs_separate_triangles' form).  The first append
+ * remembers m0 = m.  Cut t of the list, in append order, is constraint m0 + t (0-based) with
+ * right-hand side -1, the three SDP entries sigma / (2 sqrt(d_p d_q)) (d_i = b_i / a_i) on its pairs
+ * and -1 on column t of one LP block, the last cone: sigma . x - s_t = -1, s_t >= 0 -- the problem
+ * lrs_load_coo builds from instances.add_triangle_cuts' output.  The problem is rebuilt through
+ * the presolve and uploaded afresh; everything keyed on the old one is dropped.
+ * lrs_cuts_append: cuts[n][4]; a cut already in the list (or twice in the call) is skipped and
+ * *n_added (may be NULL) counts the new ones; with none new nothing changes.  A malformed cut (not
+ * 0 <= i < j < k < n, type 0 .. 3) or more than LRS_CUT_MAX_TOTAL cuts in all refuses the whole
+ * call with -2.  lrs_cuts_drop: drop[n_cuts] != 0 marks the cuts to remove; the list is compacted,
+ * order kept; *n_dropped (may be NULL); with none marked nothing changes.
+ * carry != 0 needs solver state (ranks set) and keeps it: the same ranks, the SDP cone's rows of R
+ * and LAMBDA[0, m0 + kept) the same bits, a new cut's multiplier 0 and its LP row sqrt(max(slack_t,
+ * 0)) at those rows (a kept cut's LP row: recomputed likewise by an append, kept by a drop), so the
+ * next lrs_solve_warm starts with zero residual on every cut the point satisfies.  Every other
+ * buffer is zero, and a reopt scale of the previous solve is undone first (LAMBDA divided by
+ * obj_scale).  carry == 0 leaves the ranks unset, as after a load.
+ * lrs_cuts_get: *n_cuts (may be NULL) the list's length, cuts[min(cap, n_cuts)][4] (may be NULL).
+ * lrs_cuts_state: for factor `which` (LRS_R .. LRS_V) slack[t] = 1 + ((s_ij x_ij + s_ik x_ik) +
+ * s_jk x_jk) with x_pq formed as lrs_separate_triangles forms it (the same fused multiply-add chain
+ * over the columns, the same division): for an inequality that call returns at the same factor,
+ * slack is bitwise minus its violation.  lambda[t] = LAMBDA[m0 + t].  Each may be NULL.  On the
+ * device and the context's stream, a dot a thread: the same bits on every run.  A context without
+ * cuts: 0, nothing written.
+ * lrs_round_signs and lrs_separate_triangles accept the SDP cone of a context that registered its
+ * cuts (its constraints are the n diagonal ones and exactly the list's) and act as on the plain
+ * problem at the same factor; a problem loaded with such constraints already in it stays refused.
+ * Refusals of lrs_cuts_append: -2 above, -3 a sharded context, -4 more than one SDP cone, -5 an LP
+ * block of the problem's own, -6 carry without solver state, -7 not diagonally constrained (or not
+ * by constraints 1 .. n alone), -8 a b_i <= 0, -9 a dense or constant objective, -10 dense or
+ * rank-one constraint matrices.  lrs_cuts_drop: -13 a context without cuts, -6.  lrs_cuts_state:
+ * -6, -11 a selector other than LRS_R .. LRS_V.  A refused call changes nothing.
+ * lrs_certified_bound: for such a context, with or without cuts, the weak-duality bound of the
+ * current LAMBDA in the instance file's units (lrs_result.dobj's; a reopt scale undone):
+ *   bound = b^T lambda + (sum_i d_i) min(0, lambda_min(S)) + 4 sum_t min(0, lambda_{m0 + t}),
+ * S = C - sum_i lambda_i A_i on the SDP cone: tr X = sum_i d_i is fixed by the diagonal and every
+ * slack lies in [0, 4] since |x_pq| <= 1.  lambda_min is lrs_op_dual_infeasibility's per-cone
+ * value (*lam_min, may be NULL) and *converged (may be NULL) that eigen-solve's flag: 1 when its
+ * Ritz residual met tol max(eps^(2/3), |theta|); 0 when the restart cap ran out -- the Ritz value
+ * is then only an UPPER bound of lambda_min and `bound` is not certified.  With converged = 1 the
+ * Ritz value theta is taken as lambda_min as it stands: its residual, at most 1e-2 max(eps^(2/3),
+ * |theta|), is not subtracted, so the bound is certified to within (sum_i d_i) times that.  Refusals: -3, -4, -5,
+ * -6, -7, -8, -10 as above. */
+#define LRS_CUT_MAX_TOTAL 262144
+int lrs_solve_warm(lrs_ctx *ctx, const lrs_params *p, lrs_result *res);
+int lrs_cuts_append(lrs_ctx *ctx, const int *cuts /* [n][4]: i < j < k 0-based, type 0..3 */, int n, int carry,
+                    int *n_added);
+int lrs_cuts_drop(lrs_ctx *ctx, const unsigned char *drop /* [n_cuts] */, int carry, int *n_dropped);
+int lrs_cuts_get(lrs_ctx *ctx, int *cuts, int cap, int *n_cuts);
+int lrs_cuts_state(lrs_ctx *ctx, int which, double *slack /* [n_cuts] */, double *lambda /* [n_cuts] */);
+int lrs_certified_bound(lrs_ctx *ctx, double *bound, double *lam_min, int *converged);
 /* trajectory (phase 1 then phase 2) after lrs_solve: curr and oracle ranks */
 int lrs_trajectory(lrs_ctx *ctx, int phase, int *curr_rank, int *oracle_rank, int cap);
 /* JSON like lorads_logging.c:618-712 */

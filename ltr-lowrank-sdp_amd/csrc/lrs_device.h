@@ -543,6 +543,18 @@ int launch_tri_gram(const DevCone &c, const double *X, const double *sb, double 
 int launch_tri_scan(int mode, int n, double minv, const TriPass &P, const double *x, unsigned long long *ghist,
                     unsigned long long *gcnt, unsigned *cursor, void *rec, hipStream_t st);
 
+// ---- registered triangle cuts (lrs_kernels.hip "Registered triangle cuts") ----
+// launch_cut_state: for the T cuts {i, j, k, type} (i < j < k < n, 16-byte aligned) at the cone's
+// rows X (n x ld, r columns read) with sb[n] = sqrt(b_i): slack[t] = 1 + sigma . x in
+// k_tri_gram's and k_tri_scan's arithmetic (bitwise minus the separation's violation), and, where
+// the pointers are given, lam_out[t] = lam_in[t], lp_out[t] = lp_in[t ldlp].  launch_cut_carry:
+// lam[t] = src[t] >= 0 ? lam_old[src[t]] : 0; lp[t ldlp] = (src[t] >= 0 && keep_lp) ?
+// lp_old[src[t]] : sqrt(max(slack[t], 0)).
+int launch_cut_state(int T, int r, int ld, const int *cuts, const double *X, const double *sb, const double *lam_in,
+                     const double *lp_in, int ldlp, double *slack, double *lam_out, double *lp_out, hipStream_t st);
+int launch_cut_carry(int T, const double *slack, const int *src, const double *lam_old, const double *lp_old,
+                     int keep_lp, double *lam, double *lp, int ldlp, hipStream_t st);
+
 // ---- dual infeasibility (Lanczos for lambda_min of S per cone) ----
 // y = S x over one cone's adjacency (S on the global slots, x / y cone-local vectors)
 int launch_symv(const DevProblem &P, int cone, const double *S, const double *x, double *y, hipStream_t st);

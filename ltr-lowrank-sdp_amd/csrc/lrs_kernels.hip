@@ -9894,6 +9894,10 @@ int launch_round_descent(const DevCone &c, int T, const double *wadj, unsigned l
 static_assert(kTriTile == 32 && kBlock == 256, "k_tri_gram / k_tri_scan: 32 x 32 tiles, 4 pairs a thread");
 constexpr int kTriGramCols = 32;   // factor columns of one staged chunk of k_tri_gram
 
+// The one form of x_pq's division (k_tri_gram and k_cut_state share it, so that a cut's slack is
+// the same bits as the separation's violation): the chain's sum over the product of the two roots.
+__device__ __forceinline__ double tri_x_norm(double acc, double sp, double sq) { return acc / (sp * sq); }
+
 // x[gi][gj] = <X_gi, X_gj> / (sb_gi sb_gj) over columns c < r in column order (fused multiply-adds,
 // whose products commute: x is bitwise symmetric); rows and columns n .. npad - 1 are zero.  One
 // block a 32 x 32 tile; the two row panels pass through LDS kTriGramCols columns at a time, padded
@@ -9925,7 +9929,7 @@ __global__ void __launch_bounds__(kBlock) k_tri_gram(int n, int r, int ld, int n
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int gi = i0 + ib + 8 * q;
-        x[(long)gi * npad + gj] = (gi < n && gj < n) ? acc[q] / (sb[gi] * sj) : 0.0;
+        x[(long)gi * npad + gj] = (gi < n && gj < n) ? tri_x_norm(acc[q], sb[gi], sj) : 0.0;
     }
 }
 
@@ -10055,6 +10059,96 @@ int launch_tri_scan(int mode, int n, double minv, const TriPass &P, const double
     if (mode == 0) hipLaunchKernelGGL(k_tri_scan<0>, grid, dim3(kBlock), 0, st, n, npad, S, minv, P, x, ghist, gcnt, cursor, r2);
     else if (mode == 1) hipLaunchKernelGGL(k_tri_scan<1>, grid, dim3(kBlock), 0, st, n, npad, S, minv, P, x, ghist, gcnt, cursor, r2);
     else hipLaunchKernelGGL(k_tri_scan<2>, grid, dim3(kBlock), 0, st, n, npad, S, minv, P, x, ghist, gcnt, cursor, r2);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------
+// Registered triangle cuts (no reference counterpart).  The state of every cut of
+// a context at a factor (k_cut_state) and the hand-over of that state into the rebuilt problem's
+// multipliers and LP rows (k_cut_carry).  At most 3 * LRS_CUT_MAX_TOTAL dots of at most 512 terms:
+// latency, not bandwidth, so a thread owns a whole dot and nothing is summed across lanes.
+// ------------------------------------------------------------------------
+constexpr int kCutBlockCuts = 64;                    // cuts a block: a wave a pair, a lane a cut
+constexpr int kCutBlock = 3 * kCutBlockCuts;
+
+// Thread (pair p, cut l): x_pq of the cut's p-th pair (i, j), (i, k), (j, k) with k_tri_gram's
+// arithmetic -- one fused multiply-add chain over the columns c < r in ascending order from 0.0,
+// then tri_x_norm.  The rows are ld doubles apart and 64-byte aligned (ld is a multiple of 8), so
+// four columns come as two 16-byte loads; the chain's order does not change.  After the barrier
+// the first wave combines a cut's three values as k_tri_scan does, type by type, and negates the
+// violation: slack = 1 + ((s_ij x_ij + s_ik x_ik) + s_jk x_jk) in exactly the scan's roundings.
+// lam / lprow (each may be null): the cut's multiplier and its LP row's first column, copied out.
+__global__ void __launch_bounds__(kCutBlock) k_cut_state(int T, int r, int ld, const int4 *__restrict__ cuts,
+                                                         const double *__restrict__ X, const double *__restrict__ sb,
+                                                         const double *__restrict__ lam_in,
+                                                         const double *__restrict__ lp_in, int ldlp,
+                                                         double *__restrict__ slack, double *__restrict__ lam_out,
+                                                         double *__restrict__ lp_out) {
+    __shared__ double sx[3][kCutBlockCuts];
+    const int l = threadIdx.x & (kCutBlockCuts - 1), pr = threadIdx.x / kCutBlockCuts;
+    const int t = blockIdx.x * kCutBlockCuts + l;
+    int4 cu = make_int4(0, 0, 0, 0);
+    if (t < T) {
+        cu = cuts[t];
+        const int p = pr == 2 ? cu.y : cu.x, q = pr == 0 ? cu.y : cu.z;
+        const double *xp = X + (long)p * ld, *xq = X + (long)q * ld;
+        double acc = 0.0;
+        int c = 0;
+        for (; c + 4 <= r; c += 4) {
+            const double2 a0 = *(const double2 *)(xp + c), a1 = *(const double2 *)(xp + c + 2);
+            const double2 b0 = *(const double2 *)(xq + c), b1 = *(const double2 *)(xq + c + 2);
+            acc = fma(a0.x, b0.x, acc);
+            acc = fma(a0.y, b0.y, acc);
+            acc = fma(a1.x, b1.x, acc);
+            acc = fma(a1.y, b1.y, acc);
+        }
+        for (; c < r; ++c) acc = fma(xp[c], xq[c], acc);
+        sx[pr][l] = tri_x_norm(acc, sb[p], sb[q]);
+    }
+    __syncthreads();
+    if (pr != 0 || t >= T) return;
+    const double a = sx[0][l], b = sx[1][l], cc = sx[2][l];
+    const double ab = a + b, amb = a - b;
+    double v;
+    switch (cu.w) {
+    case 0: v = -1.0 - (ab + cc); break;
+    case 1: v = -1.0 - (amb - cc); break;
+    case 2: v = -1.0 - (-amb - cc); break;
+    default: v = -1.0 - (cc - ab); break;
+    }
+    slack[t] = -v;
+    if (lam_out) lam_out[t] = lam_in ? lam_in[t] : 0.0;
+    if (lp_out) lp_out[t] = lp_in ? lp_in[(long)t * ldlp] : 0.0;
+}
+
+// The rebuilt problem's state of cut t: its multiplier lam[t] (lam points at constraint m0) is the
+// old cut src[t]'s, or 0 for a new one; its LP row's first column (the row's other columns stay
+// zero) is the old row's where keep_lp says so, else sqrt(max(slack_t, 0)).
+__global__ void __launch_bounds__(kBlock) k_cut_carry(int T, const double *__restrict__ slack, const int *__restrict__ src,
+                                                      const double *__restrict__ lam_old,
+                                                      const double *__restrict__ lp_old, int keep_lp,
+                                                      double *__restrict__ lam, double *__restrict__ lp, int ldlp) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= T) return;
+    const int s = src[t];
+    lam[t] = s >= 0 ? lam_old[s] : 0.0;
+    lp[(long)t * ldlp] = (s >= 0 && keep_lp) ? lp_old[s] : sqrt(fmax(slack[t], 0.0));
+}
+
+int launch_cut_state(int T, int r, int ld, const int *cuts, const double *X, const double *sb, const double *lam_in,
+                     const double *lp_in, int ldlp, double *slack, double *lam_out, double *lp_out, hipStream_t st) {
+    if (T <= 0) return 0;
+    hipLaunchKernelGGL(k_cut_state, dim3((T + kCutBlockCuts - 1) / kCutBlockCuts), dim3(kCutBlock), 0, st, T, r, ld,
+                       (const int4 *)cuts, X, sb, lam_in, lp_in, ldlp, slack, lam_out, lp_out);
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+int launch_cut_carry(int T, const double *slack, const int *src, const double *lam_old, const double *lp_old,
+                     int keep_lp, double *lam, double *lp, int ldlp, hipStream_t st) {
+    if (T <= 0) return 0;
+    hipLaunchKernelGGL(k_cut_carry, dim3((T + kBlock - 1) / kBlock), dim3(kBlock), 0, st, T, slack, src, lam_old, lp_old,
+                       keep_lp, lam, lp, ldlp);
     LRS_CHECK_LAUNCH();
     return 0;
 }

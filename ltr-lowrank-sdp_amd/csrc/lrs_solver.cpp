@@ -23,6 +23,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include <rccl/rccl.h>
@@ -104,6 +105,7 @@ struct GlibcRand {
 };
 
 struct AlmState {
+    bool warm = false;   // lrs_solve_warm: the ALM phase evaluates its start before iterating
     long outerIter = 0, innerIter = 0;
     double rho = 0, pobj = 1e30, dobj = 1e30, pinf1 = 1e30, pinfinf = 1e30, gap = 0;
 };
@@ -182,6 +184,23 @@ struct lrs_ctx {
     // sqrt(b), the histogram, the counters and the collected records; same life cycle
     void *tri_buf = nullptr;
     size_t tri_bytes = 0;
+    // registered triangle cuts (lrs_cuts_*).  cut_on: the problem in the context is
+    // cut_base (the plain problem's entries, rebuilt from the host problem at the first append)
+    // plus `cuts` ({i, j, k, type} each, in append order), put together by cuts_apply; every load
+    // clears it.  d_cuts / d_cut_sb: the list and sqrt(b_i / a_i) on the device; d_cut_out: slack,
+    // multiplier and LP value of every cut (3 cut_cap doubles), grown with the list.
+    struct CutBase {
+        int m0 = 0, n = 0;
+        std::vector<double> b, val;    // the plain problem: right-hand sides, entry values
+        std::vector<double> d, sb;     // X_ii = b_i / a_i by row, and its root
+        std::vector<int> con, blk, row, col;
+    };
+    bool cut_on = false;
+    CutBase cut_base;
+    std::vector<int> cuts;
+    int *d_cuts = nullptr;
+    double *d_cut_sb = nullptr, *d_cut_out = nullptr;
+    size_t cut_cap = 0;
     double *d_sendvec = nullptr;   // sharded: packed send rows of one Lanczos vector
     long sendvec_len = 0;
     // initial point cache (device layout, host copy) for the ranks it was drawn at
@@ -620,7 +639,8 @@ static void free_work(lrs_ctx *c) {
     c->walloc = false;
 }
 
-static int zero_work(lrs_ctx *c) {
+// keep_point (lrs_solve_warm): R and LAMBDA stay, everything else is reset as for a cold start
+static int zero_work(lrs_ctx *c, bool keep_point = false) {
     DevWork &W = c->W;
     const DevProblem &P = c->dp;
     const long NR = std::max(2L, P.NRpad);
@@ -632,7 +652,8 @@ static int zero_work(lrs_ctx *c) {
         {W.q2, m}, {W.M1, m}, {W.wtmp, m}, {W.cvc, (long)m * std::max(1, P.K)}, {W.ctrl, 2 * C_NCTRL},
         {W.lsres, 2 * LS_N}, {W.rec, 4L * m}, {W.tot, 32}, {W.CR, W.CR ? NR : 0}, {W.CD, W.CD ? NR : 0}};
     for (auto &z : zs)
-        if (z.p) HIPC(hipMemsetAsync(z.p, 0, sizeof(double) * z.n, c->st));
+        if (z.p && !(keep_point && (z.p == W.R || z.p == W.lam)))
+            HIPC(hipMemsetAsync(z.p, 0, sizeof(double) * z.n, c->st));
     c->head = 0; c->gcur = 0;
     c->beta[0] = c->beta[1] = c->yy[0] = c->yy[1] = 0;
     for (size_t q = 0; q < c->ring_s.size(); ++q) {   // lbfgsListLength >= 3
@@ -2204,6 +2225,22 @@ static int alm_optimize_body(lrs_ctx *c, const lrs_params *p, AlmState &st, doub
     const bool sched = p->rankSchedule && p->rankScheduleLen > 0 && p->fixedRank <= 0;
     if (sched && p->rankScheduleLen <= 1) is_rank_max = 1;
     long budget = p->almInnerBudget;
+    if (st.warm) {
+        // a warm start (lrs_solve_warm): the point is evaluated before anything iterates, and one
+        // that already meets the inner loop's phase-1 test (EXIT_PHASE1) leaves the phase here --
+        // the outer loop would otherwise skip the inner loop on rc_val <= rc_tol and raise rho
+        st.warm = false;   // the reopt rounds' ALM phases are ordinary ones
+        double pinf, obj;
+        if (op_constr_xx(c, c->W.R, nullptr, &pinf, &obj)) return -1;
+        c->pObjVal = obj / c->scaleObjHis;
+        cal_dual_obj(c);
+        c->dimPinf = pinf;
+        c->dimGap = std::fabs(c->pObjVal - c->dObjVal) / (1 + std::fabs(c->pObjVal) + std::fabs(c->dObjVal));
+        st.pobj = c->pObjVal; st.dobj = c->dObjVal; st.gap = c->dimGap;
+        st.pinf1 = c->dimPinf;
+        st.pinfinf = st.pinf1 * (1 + c->hp.bNrm1) / (1 + c->hp.bNrmInf);
+        if (st.pinfinf <= p->phase1Tol && (st.gap <= p->phase1Tol || !p->highAccMode)) goto PRINT_AND_EXIT;
+    }
 ALG_START:
     upd_cnt = 0;
     rc = 0.1;
@@ -3049,13 +3086,23 @@ void lrs_ctx_destroy(lrs_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     delete c->comm;
     for (void *q : {(void *)c->s_tickets, (void *)c->s_tmpfin, (void *)c->s_rpart, (void *)c->s_fin, (void *)c->d_sendbuf,
-                    (void *)c->d_sendvec, (void *)c->Cw0, (void *)c->Craw0, (void *)c->xwg_snap, c->round_buf, c->tri_buf})
+                    (void *)c->d_sendvec, (void *)c->Cw0, (void *)c->Craw0, (void *)c->xwg_snap, c->round_buf, c->tri_buf, (void *)c->d_cuts,
+                    (void *)c->d_cut_sb, (void *)c->d_cut_out})
         if (q) (void)hipFree(q);
     for (int *q : c->d_send_rows)
         if (q) (void)hipFree(q);
     bind_scratch(nullptr, nullptr, nullptr, nullptr);
     if (c->st) (void)hipStreamDestroy(c->st);
     delete c;
+}
+
+// a load replaces the problem: the context no longer knows any cuts
+static void cuts_forget(lrs_ctx *c) {
+    c->cut_on = false;
+    c->cuts.clear();
+    c->cut_base = lrs_ctx::CutBase();
+    if (c->d_cut_sb) (void)hipFree(c->d_cut_sb);   // sized for the old problem's rows
+    c->d_cut_sb = nullptr;
 }
 
 int lrs_load_sdpa(lrs_ctx *c, const char *path, double *read_seconds) {
@@ -3068,6 +3115,7 @@ int lrs_load_sdpa(lrs_ctx *c, const char *path, double *read_seconds) {
     if (read_seconds) *read_seconds = now_s() - t0;
     free_work(c);
     if (c->loaded) free_problem(c->dp);
+    cuts_forget(c);
     c->hp = std::move(hp);
     if (!upload_problem(c->hp, c->dp, err)) { set_err("upload: %s", err.c_str()); return -1; }
     c->loaded = true;
@@ -3090,6 +3138,7 @@ int lrs_load_coo(lrs_ctx *c, int m, int nblk, const int *dims, const double *b, 
     }
     free_work(c);
     if (c->loaded) free_problem(c->dp);
+    cuts_forget(c);
     c->hp = std::move(hp);
     if (!upload_problem(c->hp, c->dp, err)) { set_err("upload: %s", err.c_str()); return -1; }
     c->loaded = true;
@@ -3117,6 +3166,7 @@ int lrs_load_coo_rank1(lrs_ctx *c, int m, int nblk, const int *dims, const doubl
     }
     free_work(c);
     if (c->loaded) free_problem(c->dp);
+    cuts_forget(c);
     c->hp = std::move(hp);
     if (!upload_problem(c->hp, c->dp, err)) { set_err("upload: %s", err.c_str()); return -1; }
     c->loaded = true;
@@ -3574,7 +3624,11 @@ int lrs_round_dirs(unsigned long long seed, int r, int trials, double *out) {
 static int round_qualify(lrs_ctx *c, int k, std::vector<double> &sb, const char *who = "lrs_round_signs") {
     const HostCone &hc = c->hp.cones[k];
     const int n = hc.n;
-    if ((int)hc.ent.size() != n || n < 1) {
+    // a context that registered its cuts (lrs_cuts_append): the cone's other entries are exactly the
+    // cuts' three each, in constraints past the diagonal ones, and the only other cone is the cuts'
+    // LP block, which touches those constraints alone; the checks below see the diagonal part
+    const size_t ncut_ent = (c->cut_on && k == 0) ? 3 * (c->cuts.size() / 4) : 0;
+    if (hc.ent.size() != (size_t)n + ncut_ent || n < 1) {
         set_err("%s: cone %d is not diagonally constrained (%zu constraint entries on %d rows; "
                 "X_ii = b_i for every i and nothing else is required)", who, k, hc.ent.size(), n);
         return -7;
@@ -3852,7 +3906,316 @@ int lrs_separate_triangles(lrs_ctx *c, int cone, int which, int max_cuts, double
     return 0;
 }
 
-static int solve_impl(lrs_ctx *c, const lrs_params *pin, lrs_result *res) {
+// ---- registered triangle cuts (no reference counterpart)
+// Whether the context's problem can carry cuts, and at the first append its plain entries: one SDP
+// cone, diagonally constrained in lrs_round_signs' sense with constraint i the entry (i, i) and
+// m = n, no LP block of its own, the objective in the slots.  The entries are read back from the
+// host problem (C = -F0 per objective slot, the diagonal coefficients), which the presolve merged
+// and sorted: build_problem_coo of them is the problem that was loaded.
+static int cuts_qualify(lrs_ctx *c, const char *who, int carry) {
+    if (sharded(c)) { set_err("%s: sharded contexts are not supported", who); return -3; }
+    if (c->cut_on) {
+        if (carry && !c->walloc) { set_err("%s: carry needs a warm state (ranks not set)", who); return -6; }
+        return 0;
+    }
+    if (n_sdp(c) != 1) { set_err("%s: %d SDP cones (exactly one is supported)", who, n_sdp(c)); return -4; }
+    if (c->dp.lp_cone >= 0) { set_err("%s: the problem has an LP block of its own", who); return -5; }
+    if (carry && !c->walloc) { set_err("%s: carry needs a warm state (ranks not set)", who); return -6; }
+    const DevCone &dc = c->dp.cones[0];
+    if (dc.dense_c) {
+        set_err("%s: the cone keeps a %s objective out of the slots", who, dc.dense_c == 2 ? "constant" : "dense");
+        return -9;
+    }
+    if (dc.kd || dc.rp) { set_err("%s: the cone has dense or rank-one constraint matrices", who); return -10; }
+    std::vector<double> sb;
+    if (int rc = round_qualify(c, 0, sb, who)) return rc;
+    const HostCone &hc = c->hp.cones[0];
+    if (hc.ent[0].con != 0 || c->hp.m != hc.n) {
+        set_err("%s: the cone is not diagonally constrained by constraints 1 .. n alone (m = %d, n = %d, first "
+                "diagonal constraint %d)", who, c->hp.m, hc.n, hc.ent[0].con + 1);
+        return -7;
+    }
+    return 0;
+}
+static void cuts_capture_base(lrs_ctx *c) {
+    const HostCone &hc = c->hp.cones[0];
+    lrs_ctx::CutBase B;
+    B.m0 = c->hp.m;
+    B.n = hc.n;
+    B.b = c->hp.b;
+    B.sb.resize(hc.n);
+    B.d.resize(hc.n);
+    auto put = [&](int con, int row, int col, double v) {
+        B.con.push_back(con); B.blk.push_back(1); B.row.push_back(row + 1); B.col.push_back(col + 1); B.val.push_back(v);
+    };
+    for (size_t s = 0; s < hc.prow.size(); ++s)
+        if (hc.Chas[s]) put(0, hc.prow[s], hc.pcol[s], -hc.Craw[s]);
+    for (int i = 0; i < hc.n; ++i) {
+        put(i + 1, i, i, hc.ent[i].a);
+        B.d[i] = c->hp.b[i] / hc.ent[i].a;
+        B.sb[i] = std::sqrt(B.d[i]);
+    }
+    c->cut_base = std::move(B);
+}
+
+// Replace the context's problem by cut_base plus `nc` (4 ints a cut).  src[t]: the position of new
+// cut t in the current list, or -1.  carry: the rebuilt context keeps its ranks, the SDP cone's R
+// rows and LAMBDA[0, m0) bit for bit; cut t's multiplier is the old cut's or 0, its LP row the old
+// row (keep_lp, for a kept cut) or sqrt(max(slack_t, 0)) at the SDP rows.  Without carry the ranks
+// are unset, as after a load.  Fails before anything changed, except on a device error.
+static int cuts_apply(lrs_ctx *c, const std::vector<int> &nc, const std::vector<int> &src, int carry, int keep_lp) {
+    const lrs_ctx::CutBase &B = c->cut_base;
+    const int T = (int)(nc.size() / 4), To = (int)(c->cuts.size() / 4), n = B.n, m0 = B.m0;
+    std::string err;
+    HostProblem hp;
+    {
+        std::vector<int> con = B.con, blk = B.blk, row = B.row, col = B.col;
+        std::vector<double> val = B.val, b = B.b;
+        static const double sg[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
+        for (int t = 0; t < T; ++t) {
+            const int v[3] = {nc[4 * t], nc[4 * t + 1], nc[4 * t + 2]}, ty = nc[4 * t + 3];
+            const int lo[3] = {v[0], v[0], v[1]}, hi[3] = {v[1], v[2], v[2]};
+            for (int q = 0; q < 3; ++q) {   // instances.add_triangle_cuts: sigma / (2 sqrt(b_lo b_hi)), row < col
+                con.push_back(m0 + 1 + t); blk.push_back(1); row.push_back(lo[q] + 1); col.push_back(hi[q] + 1);
+                val.push_back(sg[ty][q] / (2.0 * std::sqrt(B.d[lo[q]] * B.d[hi[q]])));
+            }
+            b.push_back(-1.0);
+        }
+        for (int t = 0; t < T; ++t) {
+            con.push_back(m0 + 1 + t); blk.push_back(2); row.push_back(t + 1); col.push_back(t + 1); val.push_back(-1.0);
+        }
+        const int dims[2] = {n, -T};
+        if (!build_problem_coo(m0 + T, T > 0 ? 2 : 1, dims, b.data(), (long)con.size(), con.data(), blk.data(),
+                               row.data(), col.data(), val.data(), hp, err)) {
+            set_err("cuts: %s", err.c_str());
+            return -1;
+        }
+    }
+    // what a carry takes across: the SDP rows, LAMBDA, and the old cuts' multipliers and LP values
+    double *svR = nullptr, *svLam = nullptr, *svCut = nullptr;
+    int *dsrc = nullptr;
+    std::vector<int> ranks = c->rank;
+    auto drop_tmp = [&]() {
+        for (void *q : {(void *)svR, (void *)svLam, (void *)svCut, (void *)dsrc})
+            if (q) (void)hipFree(q);
+        svR = svLam = svCut = nullptr;
+        dsrc = nullptr;
+    };
+    struct Guard {   // every return frees the temporaries
+        decltype(drop_tmp) &f;
+        ~Guard() { f(); }
+    } guard{drop_tmp};
+    long nrows = 0;
+    if (carry) {
+        const DevCone &d0 = c->dp.cones[0];
+        nrows = (long)d0.n * d0.ld;
+        if (hipMalloc((void **)&svR, sizeof(double) * nrows) != hipSuccess ||
+            hipMalloc((void **)&svLam, sizeof(double) * m0) != hipSuccess ||
+            hipMalloc((void **)&svCut, sizeof(double) * 3 * std::max(1, To)) != hipSuccess ||
+            hipMalloc((void **)&dsrc, sizeof(int) * std::max(1, T)) != hipSuccess) {
+            drop_tmp();
+            set_err("cuts: device allocation failed");
+            return -1;
+        }
+        // from here on the context changes.  Multipliers in the unscaled objective's units first
+        if (c->c_scaled && c->scaleObjHis != 1.0)
+            OPC(launch_axpby(c->dp.m, 0.0, c->W.lam, 1.0 / c->scaleObjHis, c->W.lam, c->st));
+        HIPC(hipMemcpyAsync(svR, c->W.R + d0.foff, sizeof(double) * nrows, hipMemcpyDeviceToDevice, c->st));
+        HIPC(hipMemcpyAsync(svLam, c->W.lam, sizeof(double) * m0, hipMemcpyDeviceToDevice, c->st));
+        if (To > 0) {
+            const DevCone &dl = c->dp.cones[c->dp.lp_cone];
+            OPC(launch_cut_state(To, d0.r, d0.ld, c->d_cuts, c->W.R + d0.foff, c->d_cut_sb, c->W.lam + m0,
+                                 c->W.R + dl.foff, dl.ld, svCut, svCut + To, svCut + 2 * To, c->st));
+        }
+        if (T > 0) HIPC(hipMemcpyAsync(dsrc, src.data(), sizeof(int) * T, hipMemcpyHostToDevice, c->st));
+        HIPC(hipStreamSynchronize(c->st));
+    }
+    // everything keyed on the old problem goes: the workspace (with the captured graphs and the
+    // Lanczos buffers), the initial-point cache, the reopt copies of C, the exchange snapshot
+    free_work(c);
+    free_problem(c->dp);
+    for (double **q : {&c->Cw0, &c->Craw0, &c->xwg_snap}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    c->xwg_snap_len = 0;
+    c->c_scaled = false;
+    c->scaleObjHis = 1.0;
+    c->small_off = false;
+    c->init_cache.clear();
+    c->init_ranks.clear();
+    c->rank.clear();
+    c->rank_max.clear();
+    c->hp = std::move(hp);
+    c->cuts = nc;
+    c->cut_on = true;
+    c->cgIterCone.assign(c->hp.K, 0);
+    if (!upload_problem(c->hp, c->dp, err)) {
+        c->loaded = false;
+        drop_tmp();
+        set_err("cuts: upload: %s", err.c_str());
+        return -1;
+    }
+    if ((size_t)T > c->cut_cap || !c->d_cut_sb) {
+        for (void *q : {(void *)c->d_cuts, (void *)c->d_cut_out})
+            if (q) (void)hipFree(q);
+        c->d_cuts = nullptr; c->d_cut_out = nullptr;
+        c->cut_cap = std::max<size_t>(1024, 2 * (size_t)T);
+        HIPC(hipMalloc((void **)&c->d_cuts, sizeof(int) * 4 * c->cut_cap));
+        HIPC(hipMalloc((void **)&c->d_cut_out, sizeof(double) * 3 * c->cut_cap));
+        if (!c->d_cut_sb) {
+            HIPC(hipMalloc((void **)&c->d_cut_sb, sizeof(double) * n));
+            HIPC(h2d_sync(c, c->d_cut_sb, c->cut_base.sb.data(), sizeof(double) * n));
+        }
+    }
+    if (T > 0) HIPC(h2d_sync(c, c->d_cuts, nc.data(), sizeof(int) * 4 * (size_t)T));
+    if (!carry) return 0;
+    ranks.resize(c->dp.K);
+    if (c->dp.lp_cone >= 0) ranks[c->dp.lp_cone] = 1;
+    if (alloc_work(c, ranks)) { drop_tmp(); return -1; }
+    c->rank_max = ranks;
+    const DevCone &d0 = c->dp.cones[0];
+    HIPC(hipMemcpyAsync(c->W.R + d0.foff, svR, sizeof(double) * nrows, hipMemcpyDeviceToDevice, c->st));
+    HIPC(hipMemcpyAsync(c->W.lam, svLam, sizeof(double) * m0, hipMemcpyDeviceToDevice, c->st));
+    if (T > 0) {
+        const DevCone &dl = c->dp.cones[c->dp.lp_cone];
+        OPC(launch_cut_state(T, d0.r, d0.ld, c->d_cuts, c->W.R + d0.foff, c->d_cut_sb, nullptr, nullptr, 0, c->d_cut_out,
+                             nullptr, nullptr, c->st));
+        OPC(launch_cut_carry(T, c->d_cut_out, dsrc, svCut + To, svCut + 2 * To, keep_lp, c->W.lam + m0,
+                             c->W.R + dl.foff, dl.ld, c->st));
+    }
+    HIPC(hipStreamSynchronize(c->st));
+    drop_tmp();
+    return 0;
+}
+
+static inline unsigned long long cut_key(const int *q, int n) {
+    return (((unsigned long long)q[0] * (unsigned)n + (unsigned)q[1]) * (unsigned)n + (unsigned)q[2]) * 4ull + (unsigned)q[3];
+}
+
+int lrs_cuts_append(lrs_ctx *c, const int *cuts, int ncut, int carry, int *n_added) {
+    LRS_NEED_LOADED(c);
+    if (n_added) *n_added = 0;
+    if (ncut < 0 || (ncut > 0 && !cuts)) { set_err("lrs_cuts_append: %d cuts from a null list", ncut); return -1; }
+    if (int rc = cuts_qualify(c, "lrs_cuts_append", carry)) return rc;
+    const int n = c->hp.cones[0].n;
+    std::vector<int> nc = c->cuts, src(c->cuts.size() / 4);
+    for (size_t t = 0; t < src.size(); ++t) src[t] = (int)t;
+    std::vector<unsigned long long> have;
+    have.reserve(src.size() + ncut);
+    for (size_t t = 0; t < src.size(); ++t) have.push_back(cut_key(&nc[4 * t], n));
+    std::sort(have.begin(), have.end());
+    std::unordered_set<unsigned long long> fresh;
+    for (int t = 0; t < ncut; ++t) {
+        const int *q = cuts + 4 * (size_t)t;
+        if (!(0 <= q[0] && q[0] < q[1] && q[1] < q[2] && q[2] < n && 0 <= q[3] && q[3] < 4)) {
+            set_err("lrs_cuts_append: cut %d = {%d, %d, %d, %d} is not {i < j < k < %d, type 0 .. 3}", t, q[0], q[1],
+                    q[2], q[3], n);
+            return -2;
+        }
+        const unsigned long long key = cut_key(q, n);
+        if (std::binary_search(have.begin(), have.end(), key) || !fresh.insert(key).second) continue;
+        nc.insert(nc.end(), q, q + 4);
+        src.push_back(-1);
+    }
+    if (nc.size() / 4 > (size_t)LRS_CUT_MAX_TOTAL) {
+        set_err("lrs_cuts_append: %zu cuts in all (at most %d)", nc.size() / 4, LRS_CUT_MAX_TOTAL);
+        return -2;
+    }
+    if (fresh.empty()) return 0;   // nothing new: the context stays as it is
+    if (!c->cut_on) cuts_capture_base(c);
+    if (int rc = cuts_apply(c, nc, src, carry, 0)) {
+        if (!c->cut_on) c->cut_base = lrs_ctx::CutBase();
+        return rc;
+    }
+    if (n_added) *n_added = (int)fresh.size();
+    return 0;
+}
+
+int lrs_cuts_drop(lrs_ctx *c, const unsigned char *drop, int carry, int *n_dropped) {
+    LRS_NEED_LOADED(c);
+    if (n_dropped) *n_dropped = 0;
+    if (!c->cut_on || c->cuts.empty()) { set_err("lrs_cuts_drop: the context has no cuts"); return -13; }
+    LRS_NEED_ARG(drop);
+    if (int rc = cuts_qualify(c, "lrs_cuts_drop", carry)) return rc;
+    std::vector<int> nc, src;
+    const size_t To = c->cuts.size() / 4;
+    for (size_t t = 0; t < To; ++t) {
+        if (drop[t]) continue;
+        nc.insert(nc.end(), c->cuts.begin() + 4 * t, c->cuts.begin() + 4 * t + 4);
+        src.push_back((int)t);
+    }
+    if (src.size() == To) return 0;
+    if (int rc = cuts_apply(c, nc, src, carry, 1)) return rc;
+    if (n_dropped) *n_dropped = (int)(To - src.size());
+    return 0;
+}
+
+int lrs_cuts_get(lrs_ctx *c, int *cuts, int cap, int *n_cuts) {
+    LRS_NEED_LOADED(c);
+    const size_t T = c->cut_on ? c->cuts.size() / 4 : 0;
+    if (n_cuts) *n_cuts = (int)T;
+    if (cuts && cap > 0) memcpy(cuts, c->cuts.data(), sizeof(int) * 4 * std::min<size_t>(T, (size_t)cap));
+    return 0;
+}
+
+int lrs_cuts_state(lrs_ctx *c, int which, double *slack, double *lambda) {
+    LRS_NEED_LOADED(c);
+    const int T = c->cut_on ? (int)(c->cuts.size() / 4) : 0;
+    if (T == 0) return 0;
+    if (!c->walloc) { set_err("lrs_cuts_state: no solver state (ranks not set)"); return -6; }
+    if (which < LRS_R || which > LRS_V) { set_err("lrs_cuts_state: factor %d (LRS_R .. LRS_V)", which); return -11; }
+    const DevCone &d0 = c->dp.cones[0], &dl = c->dp.cones[c->dp.lp_cone];
+    double *out = c->d_cut_out;
+    OPC(launch_cut_state(T, d0.r, d0.ld, c->d_cuts, factor_ptr(c, which) + d0.foff, c->d_cut_sb, c->W.lam + c->cut_base.m0,
+                         factor_ptr(c, which) + dl.foff, dl.ld, out, out + T, out + 2 * T, c->st));
+    HIPC(hipStreamSynchronize(c->st));
+    if (slack) HIPC(hipMemcpy(slack, out, sizeof(double) * T, hipMemcpyDeviceToHost));
+    if (lambda) HIPC(hipMemcpy(lambda, out + T, sizeof(double) * T, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The weak-duality bound of the current multipliers (include/lrsdp.h): host composition over the
+// dual-infeasibility eigen-solve.
+int lrs_certified_bound(lrs_ctx *c, double *bound, double *lam_min, int *converged) {
+    LRS_NEED_LOADED(c);
+    LRS_NEED_ARG(bound);
+    if (sharded(c)) { set_err("lrs_certified_bound: sharded contexts are not supported"); return -3; }
+    if (n_sdp(c) != 1) { set_err("lrs_certified_bound: %d SDP cones (exactly one is supported)", n_sdp(c)); return -4; }
+    if (c->dp.lp_cone >= 0 && !c->cut_on) { set_err("lrs_certified_bound: the problem has an LP block of its own"); return -5; }
+    if (!c->walloc) { set_err("lrs_certified_bound: no solver state (ranks not set)"); return -6; }
+    const DevCone &dc = c->dp.cones[0];
+    if (dc.kd || dc.rp) { set_err("lrs_certified_bound: the cone has dense or rank-one constraint matrices"); return -10; }
+    std::vector<double> sb;
+    if (int rc = round_qualify(c, 0, sb, "lrs_certified_bound")) return rc;
+    const int m = c->dp.m, n = dc.n;
+    std::vector<double> lmin(c->dp.K, 0.0), lam(m);
+    double l1 = 0.0;
+    int conv = 1;
+    const long steps = c->dinf_steps, iters = c->dinf_iters;   // the last solve's counts stay the solve's
+    const double dtime = c->dinf_time, dtol = c->dinf_tol;
+    // the relative test alone: trl_min's absolute one (a residual that pins a solve's l_1 value to
+    // 1e-3 phase2Tol) says nothing about a lambda_min close to 0, which is where a bound is read
+    c->dinf_tol = 0.0;
+    const int drc = dual_infeasibility(c, &l1, lmin.data(), &conv);
+    c->dinf_steps = steps; c->dinf_iters = iters; c->dinf_time = dtime; c->dinf_tol = dtol;
+    if (drc) return -1;
+    HIPC(hipStreamSynchronize(c->st));
+    HIPC(hipMemcpy(lam.data(), c->W.lam, sizeof(double) * m, hipMemcpyDeviceToHost));
+    const double s = c->scaleObjHis;   // a reopt round scaled C and the multipliers alike
+    double bl = 0.0, tr = 0.0, neg = 0.0;
+    for (int i = 0; i < m; ++i) bl += c->hp.b[i] * lam[i];
+    for (int i = 0; i < n; ++i) tr += c->hp.b[c->hp.cones[0].ent[i].con] / c->hp.cones[0].ent[i].a;
+    const int m0 = c->cut_on ? c->cut_base.m0 : m;
+    for (int t = m0; t < m; ++t) neg += std::min(0.0, lam[t]);
+    *bound = bl / s + tr * std::min(0.0, lmin[0] / s) + 4.0 * neg / s;
+    if (lam_min) *lam_min = lmin[0] / s;
+    if (converged) *converged = conv;
+    return 0;
+}
+
+static int warm_reset(lrs_ctx *c, const lrs_params *p);
+static int solve_impl(lrs_ctx *c, const lrs_params *pin, lrs_result *res, bool warm = false) {
     lrs_params prm = *pin;
     lrs_params *p = &prm;
     p->rhoCellingADMM = p->rhoMax * 200;   // main.c:350
@@ -3872,17 +4235,26 @@ static int solve_impl(lrs_ctx *c, const lrs_params *pin, lrs_result *res) {
     }
     c->lbfgsL = p->lbfgsListLength;
     c->dinf_time = 0.0;
+    // a warm start's multipliers back in the unscaled objective's units (obj_scale multiplied them
+    // by every reopt factor along with C; obj_unscale restores C alone)
+    if (warm && c->c_scaled && c->scaleObjHis != 1.0)
+        OPC(launch_axpby(c->dp.m, 0.0, c->W.lam, 1.0 / c->scaleObjHis, c->W.lam, c->st));
     if (obj_unscale(c)) return -1;   // a previous solve's reopt scaled C on the device
-    std::vector<int> r, rm;
-    determine_rank(c, p, r, rm);
-    if (alloc_work(c, r)) return -1;
-    c->rank_max = rm;
-    if (init_point(c)) return -1;
+    if (warm) {
+        if (warm_reset(c, p)) return -1;
+    } else {
+        std::vector<int> r, rm;
+        determine_rank(c, p, r, rm);
+        if (alloc_work(c, r)) return -1;
+        c->rank_max = rm;
+        if (init_point(c)) return -1;
+    }
     c->t1c.clear(); c->t1o.clear(); c->t2c.clear(); c->t2o.clear();
     c->naive_warned = false;
     c->scaleObjHis = 1.0;
     c->pObjVal = c->dObjVal = 0;
     AlmState alm;
+    alm.warm = warm;
     AdmmState admm;
     double rho = p->initRho;
     if (rho == 0) {   // initial_solver_state, data/lorads_solver.c:1599-1606
@@ -3909,6 +4281,9 @@ static int solve_impl(lrs_ctx *c, const lrs_params *pin, lrs_result *res) {
         const double ta = now_s();
         int arc = admm_optimize(c, p, admm, p->maxADMMIter, tss);
         if (arc < 0) return -1;
+        // a warm start that meets phase2Tol as it stands: the ADMM phase returns before its first
+        // evaluation (as it does for any such ALM state) and the point's objectives are the ALM's
+        if (warm && admm.iter == 0 && admm.pobj == 1e30) { admm.pobj = alm.pobj; admm.dobj = alm.dobj; }
         t_admm = now_s() - ta;
         // reoptLevel >= 1 (main.c:491-513): one reopt round while neither phase met phase2Tol
         const double reopt_param = 5;
@@ -4006,6 +4381,48 @@ int lrs_solve(lrs_ctx *c, const lrs_params *p, lrs_result *res) {
     LRS_NEED_ARG(p);
     LRS_NEED_ARG(res);
     return solve_impl(c, p, res);
+}
+
+// The workspace of a warm start (lrs_solve_warm): rank_max by determine_rank's rule for the current
+// m, the current ranks clipped to it (a clipped cone keeps its leading columns), R and LAMBDA kept,
+// everything else as after a cold start's alloc_work.
+static int warm_reset(lrs_ctx *c, const lrs_params *p) {
+    std::vector<int> r, rm;
+    determine_rank(c, p, r, rm);
+    std::vector<int> nr = c->rank;
+    bool clipped = false;
+    for (int k = 0; k < c->dp.K; ++k)
+        if (nr[k] > rm[k]) { nr[k] = rm[k]; clipped = true; }
+    c->rank_max = rm;
+    if (!clipped) return zero_work(c, true);
+    long NRo = 0, NRn = 0;
+    for (int k = 0; k < c->dp.K; ++k) { NRo += (long)c->dp.cones[k].n * c->rank[k]; NRn += (long)c->dp.cones[k].n * nr[k]; }
+    std::vector<double> R(NRo), Rn(NRn), lam(c->dp.m);
+    if (factor_fetch(c, c->W.R, R.data())) return -1;
+    HIPC(hipMemcpy(lam.data(), c->W.lam, sizeof(double) * c->dp.m, hipMemcpyDeviceToHost));
+    long so = 0, dn = 0;
+    for (int k = 0; k < c->dp.K; ++k) {   // column-major: the leading columns are the leading entries
+        const long n = c->dp.cones[k].n;
+        std::copy(R.begin() + so, R.begin() + so + n * nr[k], Rn.begin() + dn);
+        so += n * c->rank[k];
+        dn += n * nr[k];
+    }
+    if (alloc_work(c, nr)) return -1;
+    if (factor_put(c, c->W.R, Rn.data())) return -1;
+    HIPC(h2d_sync(c, c->W.lam, lam.data(), sizeof(double) * c->dp.m));
+    return 0;
+}
+
+int lrs_solve_warm(lrs_ctx *c, const lrs_params *p, lrs_result *res) {
+    LRS_NEED_LOADED(c);
+    LRS_NEED_ARG(p);
+    LRS_NEED_ARG(res);
+    if (sharded(c)) { set_err("lrs_solve_warm: sharded contexts are not supported"); return -3; }
+    if (!c->walloc || c->rank.size() != (size_t)c->dp.K) {
+        set_err("lrs_solve_warm: no solver state to start from (ranks not set)");
+        return -6;
+    }
+    return solve_impl(c, p, res, true);
 }
 
 // ---- batched solves

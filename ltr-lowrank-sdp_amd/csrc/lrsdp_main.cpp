@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -77,6 +78,9 @@ struct Flags {
     int triangleCuts = 0;
     double triangleMinViol = 0.0;
     std::string triangleFile;
+    int cutRounds = 0;
+    bool cutDrop = false;
+    double cutDropSlack = 0.0;
 };
 static void parse_flags(int argc, char **argv, Flags &F) {
     lrs_params &p = F.p;
@@ -101,7 +105,8 @@ static void parse_flags(int argc, char **argv, Flags &F) {
         {"roundTrials", required_argument, 0, 2006}, {"roundSeed", required_argument, 0, 2007},
         {"roundLocalSearch", required_argument, 0, 2008}, {"roundFile", required_argument, 0, 2009},
         {"triangleCuts", required_argument, 0, 2010}, {"triangleMinViol", required_argument, 0, 2011},
-        {"triangleFile", required_argument, 0, 2012}, {0, 0, 0, 0}};
+        {"triangleFile", required_argument, 0, 2012}, {"cutRounds", required_argument, 0, 2013},
+        {"cutDropSlack", required_argument, 0, 2014}, {0, 0, 0, 0}};
     int opt, li = 0;
     optind = 0;   // a fresh scan (one per manifest line)
     while ((opt = getopt_long(argc, argv, "r:", opts, &li)) != -1) {
@@ -146,6 +151,8 @@ static void parse_flags(int argc, char **argv, Flags &F) {
         case 2010: F.triangleCuts = atoi(optarg); break;
         case 2011: F.triangleMinViol = atof(optarg); break;
         case 2012: F.triangleFile = optarg; break;
+        case 2013: F.cutRounds = atoi(optarg); break;
+        case 2014: F.cutDrop = true; F.cutDropSlack = atof(optarg); break;
         default: break;   // unknown flags: getopt already printed a message; ignored like main.c
         }
     }
@@ -192,12 +199,14 @@ static void json_append(const char *jsonFile, const std::string &obj) {
 // same seed), the best values summed (cones with only diagonal constraints are independent).  On
 // success the JSON at jsonFile (if any) gains "rounding" before its closing brace and roundFile
 // receives the assignment; a cone that does not qualify leaves both as they are (one stderr line).
-static void round_and_report(lrs_ctx *ctx, const Flags &F, const char *jsonFile) {
+// sdp_only: after cut rounds the last cone is the cuts' LP block, which is not rounded.
+static void round_and_report(lrs_ctx *ctx, const Flags &F, const char *jsonFile, bool sdp_only = false) {
     if (F.roundTrials <= 0) return;
     int K = 0;
     lrs_problem_info(ctx, nullptr, &K, nullptr, nullptr, nullptr);
     std::vector<int> dims(K > 0 ? K : 1);
     lrs_problem_info(ctx, nullptr, nullptr, dims.data(), nullptr, nullptr);
+    if (sdp_only) K = 1;
     std::vector<signed char> x;
     std::vector<int> best(K, 0);
     double value = 0.0, secs = 0.0;
@@ -317,6 +326,114 @@ static void triangles_and_report(lrs_ctx *ctx, const Flags &F, const char *jsonF
     json_append(jsonFile, obj);
 }
 
+// --cutRounds N (with --triangleCuts K) after the first solve: the cutting-plane loop of DESIGN.md
+// §4.14 in the one context.  Round 0 is the solve just done; each later round separates K + E
+// inequalities at R (E: registered cuts violated by more than --triangleMinViol), takes the K most
+// violated that are not registered, stops when none is new, drops cuts with slack > --cutDropSlack
+// and a multiplier >= 0 (if given), appends with carry and re-solves warm.  `r` ends as the last
+// solve's result; `rounds` receives the JSON array's text; triangleFile the final cut list as `i j k
+// type violation` (1-based, the violation at the final R: minus the cut's slack).  A problem that
+// does not qualify keeps the first solve and costs one stderr line.
+static void cut_rounds(lrs_ctx *ctx, const Flags &F, lrs_result &r, std::string &rounds) {
+    auto now = []() {
+        timespec t;
+        clock_gettime(CLOCK_MONOTONIC, &t);
+        return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+    };
+    auto num = [](double v) {
+        char b[40];
+        snprintf(b, sizeof(b), "%.16e", v);
+        return std::string(b);
+    };
+    const int K = F.triangleCuts < LRS_TRI_MAX_K ? F.triangleCuts : LRS_TRI_MAX_K;
+    int ncut = 0;
+    auto record = [&](double t0, int added, int dropped, long long nviol, double maxv) -> bool {
+        double bound = 0.0, best = 0.0;
+        int conv = 0;
+        if (lrs_certified_bound(ctx, &bound, nullptr, &conv)) return false;
+        if (F.roundTrials > 0 && lrs_round_signs(ctx, 0, LRS_R, F.roundTrials, nullptr, F.roundSeed, F.roundLocalSearch, 0,
+                                                 nullptr, nullptr, nullptr, &best, nullptr, nullptr))
+            return false;
+        lrs_cuts_get(ctx, nullptr, 0, &ncut);
+        std::string o = rounds.empty() ? "\n    {" : ",\n    {";
+        o += "\"n_cuts\": " + std::to_string(ncut) + ", \"n_added\": " + std::to_string(added) + ", \"n_dropped\": " +
+             std::to_string(dropped) + ", \"n_violated\": " + std::to_string(nviol) + ", \"max_violation\": " + num(maxv) +
+             ", \"pobj\": " + num(r.pobj) + ", \"dobj\": " + num(r.dobj) + ", \"certified_bound\": " + num(bound) +
+             ", \"bound_converged\": " + (conv ? "true" : "false") + ", \"alm_inner\": " + std::to_string(r.alm_inner) +
+             ", \"admm_iter\": " + std::to_string(r.admm_iter);
+        if (F.roundTrials > 0) o += ", \"best_value\": " + num(best);
+        o += ", \"time_sec\": " + num(now() - t0) + "}";
+        rounds += o;
+        printf("Cut round: %d cuts (+%d -%d), %lld violated (largest %.6e), pObj %.10e, certified bound %.10e%s\n", ncut,
+               added, dropped, nviol, maxv, r.pobj, bound, conv ? "" : " (eigen-solve not converged)");
+        return true;
+    };
+    double t0 = now() - r.solve_time;
+    long long nviol = 0;
+    double maxv = 0.0;
+    if (lrs_separate_triangles(ctx, 0, LRS_R, 1, F.triangleMinViol, nullptr, nullptr, nullptr, &nviol, &maxv) ||
+        !record(t0, 0, 0, nviol, maxv)) {
+        fprintf(stderr, "[lrsdp] cut rounds skipped: %s\n", lrs_last_error());
+        rounds.clear();
+        return;
+    }
+    std::vector<int> have, cand;
+    std::vector<double> slack, lam;
+    for (int rnd = 0; rnd < F.cutRounds; ++rnd) {
+        t0 = now();
+        lrs_cuts_get(ctx, nullptr, 0, &ncut);
+        have.assign(4 * (size_t)(ncut > 0 ? ncut : 1), 0);
+        slack.assign(ncut > 0 ? ncut : 1, 0.0);
+        lam.assign(ncut > 0 ? ncut : 1, 0.0);
+        lrs_cuts_get(ctx, have.data(), ncut, nullptr);
+        if (lrs_cuts_state(ctx, LRS_R, slack.data(), lam.data())) break;
+        int extra = 0;
+        for (int t = 0; t < ncut; ++t) extra += slack[t] < -F.triangleMinViol ? 1 : 0;
+        const int want = K + extra < LRS_TRI_MAX_K ? K + extra : LRS_TRI_MAX_K;
+        cand.assign(4 * (size_t)want, 0);
+        int got = 0;
+        if (lrs_separate_triangles(ctx, 0, LRS_R, want, F.triangleMinViol, cand.data(), nullptr, &got, &nviol, &maxv)) break;
+        std::vector<std::vector<int>> known;
+        for (int t = 0; t < ncut; ++t) known.push_back({have[4 * t], have[4 * t + 1], have[4 * t + 2], have[4 * t + 3]});
+        std::sort(known.begin(), known.end());
+        std::vector<int> fresh;
+        for (int t = 0; t < got && (int)fresh.size() < 4 * K; ++t) {
+            const std::vector<int> q(cand.begin() + 4 * t, cand.begin() + 4 * t + 4);
+            if (!std::binary_search(known.begin(), known.end(), q)) fresh.insert(fresh.end(), q.begin(), q.end());
+        }
+        if (fresh.empty()) break;
+        int dropped = 0, added = 0;
+        if (F.cutDrop && ncut > 0) {
+            std::vector<unsigned char> mark(ncut, 0);
+            for (int t = 0; t < ncut; ++t) mark[t] = slack[t] > F.cutDropSlack && lam[t] >= 0.0;
+            if (lrs_cuts_drop(ctx, mark.data(), 1, &dropped)) break;
+        }
+        lrs_result rr;
+        if (lrs_cuts_append(ctx, fresh.data(), (int)(fresh.size() / 4), 1, &added) || lrs_solve_warm(ctx, &F.p, &rr)) {
+            fprintf(stderr, "[lrsdp] cut round %d failed: %s\n", rnd + 1, lrs_last_error());
+            break;
+        }
+        rr.read_time = r.read_time;
+        r = rr;
+        if (!record(t0, added, dropped, nviol, maxv)) break;
+    }
+    if (!F.triangleFile.empty()) {
+        lrs_cuts_get(ctx, nullptr, 0, &ncut);
+        have.assign(4 * (size_t)(ncut > 0 ? ncut : 1), 0);
+        slack.assign(ncut > 0 ? ncut : 1, 0.0);
+        lrs_cuts_get(ctx, have.data(), ncut, nullptr);
+        lrs_cuts_state(ctx, LRS_R, slack.data(), nullptr);
+        FILE *f = fopen(F.triangleFile.c_str(), "w");
+        if (!f) fprintf(stderr, "[lrsdp] cannot open %s\n", F.triangleFile.c_str());
+        else {
+            for (int t = 0; t < ncut; ++t)
+                fprintf(f, "%d %d %d %d %.17g\n", have[4 * t] + 1, have[4 * t + 1] + 1, have[4 * t + 2] + 1, have[4 * t + 3],
+                        -slack[t]);
+            fclose(f);
+        }
+    }
+}
+
 // --batch FILE: load every line's instance, one lrs_solve_batch, one JSON each
 static int run_batch(const Flags &base, const char *prog) {
     FILE *f = fopen(base.batchFile.c_str(), "r");
@@ -332,6 +449,7 @@ static int run_batch(const Flags &base, const char *prog) {
         bool ok = false;
     };
     std::vector<Job *> jobs;
+    bool cut_flag = base.cutRounds > 0;
     std::string text;
     char buf[4096];
     size_t nr;
@@ -368,8 +486,10 @@ static int run_batch(const Flags &base, const char *prog) {
         parse_flags((int)av.size() - 1, av.data(), j->F);
         j->F.jsonFile = tok[1];
         finish_flags(j->F, j->sched);
+        cut_flag = cut_flag || j->F.cutRounds > 0;
         jobs.push_back(j);
     }
+    if (cut_flag) fprintf(stderr, "[lrsdp] --cutRounds is ignored with --batch\n");
     if ((int)jobs.size() > LRS_BATCH_MAX) {
         fprintf(stderr, "[lrsdp] batch file %s: %zu instances (at most %d)\n", base.batchFile.c_str(), jobs.size(),
                 LRS_BATCH_MAX);
@@ -486,6 +606,10 @@ int main(int argc, char **argv) {
         lrs_ctx_destroy(ctx);
         return 0;
     }
+    std::string rounds;
+    const bool cut_mode = F.cutRounds > 0;
+    if (cut_mode && F.triangleCuts <= 0) fprintf(stderr, "[lrsdp] --cutRounds needs --triangleCuts K; ignored\n");
+    else if (cut_mode) cut_rounds(ctx, F, r, rounds);
     printf("-----------------------------------------------------------------------\n");
     // LORADSEndProgram, data/lorads_solver.c:1307-1333
     if (r.status == 3) printf("End Program due to reaching `the maximum number of iterations`:\n");
@@ -514,8 +638,10 @@ int main(int argc, char **argv) {
         else
             printf("JSON output written to: %s\n", jsonFile);
     }
-    round_and_report(ctx, F, jsonFile);
-    triangles_and_report(ctx, F, jsonFile);
+    round_and_report(ctx, F, jsonFile, !rounds.empty());
+    // after cut rounds the triangles' report is the rounds' (the file holds the final cut list)
+    if (rounds.empty()) triangles_and_report(ctx, F, jsonFile);
+    else if (jsonFile) json_append(jsonFile, ",\n  \"cut_rounds\": [" + rounds + "\n  ]\n}\n");
     lrs_ctx_destroy(ctx);
     return 0;
 }

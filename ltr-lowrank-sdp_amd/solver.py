@@ -170,6 +170,12 @@ def load_library(path=None):
                                       C.POINTER(C.c_ulonglong), ip, dp, C.POINTER(C.c_byte), ip]),
         "lrs_separate_triangles": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, ip, dp, ip,
                                              C.POINTER(C.c_longlong), dp]),
+        "lrs_solve_warm": (C.c_int, [vp, C.POINTER(Params), C.POINTER(Result)]),
+        "lrs_cuts_append": (C.c_int, [vp, ip, C.c_int, C.c_int, ip]),
+        "lrs_cuts_drop": (C.c_int, [vp, C.POINTER(C.c_ubyte), C.c_int, ip]),
+        "lrs_cuts_get": (C.c_int, [vp, ip, C.c_int, ip]),
+        "lrs_cuts_state": (C.c_int, [vp, C.c_int, dp, dp]),
+        "lrs_certified_bound": (C.c_int, [vp, dp, dp, ip]),
         "lrs_shard_plan": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_long), ip, ip, ip, ip, ip, ip, ip]),
     }
     for name, (res, args) in sig.items():
@@ -229,6 +235,16 @@ class TriangleError(RuntimeError):
 
     def __init__(self, code, msg):
         super().__init__(f"separate_triangles ({code}): {msg}")
+        self.code = code
+        self.message = msg
+
+
+class CutError(RuntimeError):
+    """A refused Solver.solve_warm / append_cuts / drop_cuts / cuts_state / certified_bound: `code`
+    is the library's negative return value."""
+
+    def __init__(self, what, code, msg):
+        super().__init__(f"{what} ({code}): {msg}")
         self.code = code
         self.message = msg
 
@@ -558,6 +574,129 @@ class Solver:
         res = Result()
         self._check(self.lib.lrs_solve(self.ctx, C.byref(p), C.byref(res)), "solve")
         return res.as_dict()
+
+    # ---- cutting-plane rounds in one context (include/lrsdp.h lrs_solve_warm .. lrs_certified_bound,
+    # DESIGN.md §4.14)
+    def _cut_check(self, rc, what):
+        if rc != 0:
+            raise CutError(what, rc, self.lib.lrs_last_error().decode())
+
+    def _refresh_info(self):
+        """m, K and dims after the cut list changed the problem."""
+        m, k = C.c_int(), C.c_int()
+        self._check(self.lib.lrs_problem_info(self.ctx, C.byref(m), C.byref(k), None, None, None), "info")
+        dims = (C.c_int * max(1, k.value))()
+        ns, nz = C.c_long(), C.c_long()
+        self._check(self.lib.lrs_problem_info(self.ctx, None, None, dims, C.byref(ns), C.byref(nz)), "info")
+        self.m, self.K, self.dims = m.value, k.value, list(dims)[:k.value]
+        self.nslots, self.nnz = ns.value, nz.value
+        self.ranks = None
+
+    def solve_warm(self, **kw):
+        """lrs_solve's flow started from the context's current R and LAMBDA at its current ranks
+        (everything else as a cold start).  A refusal raises CutError."""
+        p = default_params(**kw)
+        res = Result()
+        self._cut_check(self.lib.lrs_solve_warm(self.ctx, C.byref(p), C.byref(res)), "solve_warm")
+        return res.as_dict()
+
+    def append_cuts(self, cuts, carry=True):
+        """Register triangle inequalities (rows {i, j, k, type} as separate_triangles returns them)
+        as constraints with LP slacks, in place; cuts already present are skipped.  carry: keep
+        the ranks, the SDP rows of R and LAMBDA, new multipliers 0, LP rows sqrt(max(slack, 0)).
+        Returns the number added."""
+        a = np.ascontiguousarray(np.asarray(cuts, dtype=np.int32).reshape(-1, 4))
+        na = C.c_int()
+        self._cut_check(self.lib.lrs_cuts_append(self.ctx, a.ctypes.data_as(C.POINTER(C.c_int)), a.shape[0],
+                                                 1 if carry else 0, C.byref(na)), "append_cuts")
+        self._refresh_info()
+        return na.value
+
+    def drop_cuts(self, mask, carry=True):
+        """Remove the cuts whose entry of `mask` (one per registered cut) is true; order kept.
+        Returns the number dropped."""
+        k = np.ascontiguousarray(np.asarray(mask).astype(bool).astype(np.uint8).ravel())
+        nc = C.c_int()
+        self._check(self.lib.lrs_cuts_get(self.ctx, None, 0, C.byref(nc)), "cuts_get")
+        if nc.value and k.size != nc.value:
+            raise ValueError(f"drop_cuts: mask of {k.size} for {nc.value} cuts")
+        nd = C.c_int()
+        self._cut_check(self.lib.lrs_cuts_drop(self.ctx, k.ctypes.data_as(C.POINTER(C.c_ubyte)), 1 if carry else 0,
+                                               C.byref(nd)), "drop_cuts")
+        self._refresh_info()
+        return nd.value
+
+    def cuts(self):
+        """The registered cuts, (n_cuts, 4) int32 in append order."""
+        nc = C.c_int()
+        self._check(self.lib.lrs_cuts_get(self.ctx, None, 0, C.byref(nc)), "cuts_get")
+        out = np.zeros((max(1, nc.value), 4), dtype=np.int32)
+        self._check(self.lib.lrs_cuts_get(self.ctx, out.ctypes.data_as(C.POINTER(C.c_int)), nc.value, C.byref(nc)),
+                    "cuts_get")
+        return out[:nc.value].copy()
+
+    def cuts_state(self, which=R):
+        """(slack, lambda) of every registered cut at factor `which`: slack = 1 + sigma . x in the
+        separation's arithmetic (bitwise minus its violation), lambda the cut's multiplier."""
+        nc = C.c_int()
+        self._check(self.lib.lrs_cuts_get(self.ctx, None, 0, C.byref(nc)), "cuts_get")
+        slack, lam = np.zeros(max(1, nc.value)), np.zeros(max(1, nc.value))
+        self._cut_check(self.lib.lrs_cuts_state(self.ctx, which, _dptr(slack), _dptr(lam)), "cuts_state")
+        return slack[:nc.value].copy(), lam[:nc.value].copy()
+
+    def certified_bound(self):
+        """(bound, lambda_min, converged): the weak-duality bound of the current multipliers in the
+        instance file's units; certified only when converged (else lambda_min is a Ritz value, an
+        upper bound of the smallest eigenvalue)."""
+        b, lm, cv = C.c_double(), C.c_double(), C.c_int()
+        self._cut_check(self.lib.lrs_certified_bound(self.ctx, C.byref(b), C.byref(lm), C.byref(cv)),
+                        "certified_bound")
+        return b.value, lm.value, bool(cv.value)
+
+    def cut_loop(self, rounds, max_cuts, min_violation=1e-6, drop_slack=None, round_trials=0, **solve_kw):
+        """Cutting-plane rounds in this context: round 0 is the plain solve(); each later round
+        separates max_cuts + E inequalities at R (E: registered cuts violated by more than
+        min_violation), takes the max_cuts most violated that are not registered yet, stops when
+        none is new, optionally drops cuts with slack > drop_slack and lambda >= 0, appends with
+        carry and calls solve_warm().  Returns one dict a round: n_cuts, n_added, n_dropped,
+        n_violated, max_violation, pobj, dobj, certified_bound, bound_converged, alm_inner,
+        admm_iter, time_sec, and best_value when round_trials > 0."""
+        import time as _time
+        out = []
+
+        def record(res, t0, n_added, n_dropped, n_violated, max_violation):
+            bound, _, conv = self.certified_bound()
+            rec = {"n_cuts": int(self.cuts().shape[0]), "n_added": int(n_added), "n_dropped": int(n_dropped),
+                   "n_violated": int(n_violated), "max_violation": float(max_violation), "pobj": res["pobj"],
+                   "dobj": res["dobj"], "certified_bound": bound, "bound_converged": conv,
+                   "alm_inner": res["alm_inner"], "admm_iter": res["admm_iter"]}
+            if round_trials > 0:
+                rec["best_value"] = self.round_signs(int(round_trials))["best_value"]
+            rec["time_sec"] = _time.perf_counter() - t0
+            out.append(rec)
+
+        t0 = _time.perf_counter()
+        res = self.solve(**solve_kw)
+        _, _, nv, mv = self.separate_triangles(1, min_violation)
+        record(res, t0, 0, 0, nv, mv)
+        for _ in range(int(rounds)):
+            t0 = _time.perf_counter()
+            have = self.cuts()
+            slack, lam = self.cuts_state()
+            extra = int((slack < -min_violation).sum())
+            want = min(int(max_cuts) + extra, 65536)
+            cand, _, nv, mv = self.separate_triangles(want, min_violation)
+            known = {tuple(int(v) for v in q) for q in have}
+            new = [q for q in cand if tuple(int(v) for v in q) not in known][:int(max_cuts)]
+            if not new:
+                break
+            nd = 0
+            if drop_slack is not None and have.shape[0]:
+                nd = self.drop_cuts((slack > drop_slack) & (lam >= 0.0), carry=True)
+            na = self.append_cuts(np.asarray(new, dtype=np.int32), carry=True)
+            res = self.solve_warm(**solve_kw)
+            record(res, t0, na, nd, nv, mv)
+        return out
 
     def trajectory(self, phase):
         n = self.lib.lrs_trajectory(self.ctx, phase, None, None, 0)
