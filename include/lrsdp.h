@@ -26,8 +26,10 @@
 /* ABI revision, also in lrs_version()'s string.  2: lrs_op_admm_half takes (cone, side) and
  * refreshes the cone's constraint values itself (was: the whole sweep's first half-step);
  * lrs_op_alm_update, lrs_op_adjoint, lrs_op_auv and lrs_op_dimacs added.
- * 3: lrs_solve_warm, lrs_cuts_append / _drop / _get / _state and lrs_certified_bound added. */
-#define LRSDP_ABI_VERSION 3
+ * 3: lrs_solve_warm, lrs_cuts_append / _drop / _get / _state and lrs_certified_bound added.
+ * 4: lrs_sym_eig, lrs_factor_spectrum, lrs_factor_compress, lrs_set_rank_shrink and
+ * lrs_compress_timing added (lrs_params and lrs_result unchanged). */
+#define LRSDP_ABI_VERSION 4
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -384,6 +386,56 @@ int lrs_cuts_drop(lrs_ctx *ctx, const unsigned char *drop /* [n_cuts] */, int ca
 int lrs_cuts_get(lrs_ctx *ctx, int *cuts, int cap, int *n_cuts);
 int lrs_cuts_state(lrs_ctx *ctx, int which, double *slack /* [n_cuts] */, double *lambda /* [n_cuts] */);
 int lrs_certified_bound(lrs_ctx *ctx, double *bound, double *lam_min, int *converged);
+/* ---- Rank reduction: the factors rotated to the principal axes of their Gram.
+ * No reference counterpart.  With G = X^T X = Q diag(w) Q^T, w descending, X Q has the same X X^T;
+ * its leading k columns are the best rank-k approximation and the trace lost is sum_{j >= k} w_j.
+ * lrs_sym_eig (host only, no context, like lrs_round_dirs): a symmetric r x r (row- or column-
+ * major, it is symmetric; the mean of the two triangles is taken), w[r] its eigenvalues in
+ * descending order, q (may be NULL) column-major r x r, column j the unit eigenvector of w[j] with
+ * its component of largest magnitude positive (the first one on a tie).  Householder
+ * tridiagonalisation and implicit QL with accumulated vectors; the same bits on every call.  -2:
+ * r < 1 or a NULL a / w.
+ * `which`: LRS_R takes the source R, LRS_U the source (U + V) / 2, the phase-2 point; anything else
+ * is refused with -11.
+ * lrs_factor_spectrum changes nothing: per cone the device Gram (k_gram), then lrs_sym_eig's
+ * routine.  eigs[sum_k r_k] cone by cone, descending, small negative values as they come; the LP
+ * cone contributes its one 1 x 1 Gram entry.  counts[k]: eigenvalues > rel_tol times the cone's
+ * largest.  Each may be NULL.
+ * lrs_factor_compress: for each SDP cone k_new = new_ranks[k] when given and > 0, else min(r,
+ * max(1, count(rel_tol) + slack)); the LP cone stays at rank 1 and its rows are copied bit for bit
+ * (LRS_R).  Every cone is rotated, also where k_new = r.  Afterwards the context's ranks are the new
+ * ones (rank_max untouched: AUG_RANK can grow them again), R = U = V = the compressed source,
+ * bitwise equal, LAMBDA is kept bit for bit, every other work buffer is zero as after lrs_set_rank,
+ * and what is keyed on the workspace is dropped as lrs_set_rank drops it.  A reopt scale is left as
+ * it is.  The factors do not go through the host: the old R, U, V stay alive across the
+ * reallocation, k_rot (FP64 matrix cores) writes old -> new, then they are freed (peak memory: the
+ * new workspace plus three old factors; host traffic: the r x r Grams down, Q up).  Outputs, each
+ * may be NULL: ranks_out[K]; eigs as above (at the OLD ranks); lost[K] = the sum of the dropped
+ * eigenvalues, max(., 0) each; q cone by cone, column-major r_k x r_k (old ranks).
+ * Refusals (nothing changed): -3 a sharded context, -6 ranks not set, -11 a bad selector, -2 a
+ * new_ranks[k] < 0 or above the current rank, an LP entry other than 0 or 1, rel_tol outside
+ * [0, 1), slack < 0 (-1: the header's general failures).  Contexts with registered cuts, dense-A,
+ * rank-one and dense-objective cones are accepted: only the factor layout changes.
+ * lrs_solve_warm clips an over-wide start to its leading columns: compress first, then the leading
+ * columns are the principal ones.
+ * lrs_set_rank_shrink(rel_tol, slack): rel_tol <= 0 is off, the default.  On, lrs_solve and
+ * lrs_solve_warm do this once, right before the ALM-to-ADMM hand-over, on an unsharded context
+ * whose time limit has not hit: the counts of R are taken, and if some cone's min(r, max(1, count +
+ * slack)) is below its rank the point is compressed to those ranks (log line "rank shrink: a ->
+ * b").  The phase-2 trajectory and final_rank then show the lower ranks; the reopt rounds run on
+ * from there.  lrs_solve_batch ignores the setting: batch members keep their ranks.  Off, no output
+ * differs by a byte.  -2: rel_tol >= 1 or NaN, slack < 0.
+ * lrs_compress_timing: the last lrs_factor_compress's k_rot launches between two HIP events (ms)
+ * and their algorithmic bytes, 8 n (r + k) per cone (8 n (2 r + k) from LRS_U). */
+int lrs_sym_eig(int r, const double *a, double *w, double *q);
+int lrs_factor_spectrum(lrs_ctx *ctx, int which, double rel_tol,
+                        double *eigs /* [sum_k r_k], cone by cone, descending */,
+                        int *counts /* [K]: eigenvalues > rel_tol * the cone's largest */);
+int lrs_factor_compress(lrs_ctx *ctx, int which, const int *new_ranks /* [K] or NULL */, double rel_tol, int slack,
+                        int *ranks_out /* [K] */, double *eigs /* as above, may be NULL */,
+                        double *lost /* [K], may be NULL */, double *q /* may be NULL */);
+int lrs_set_rank_shrink(lrs_ctx *ctx, double rel_tol, int slack);
+int lrs_compress_timing(lrs_ctx *ctx, double *rot_ms, double *rot_bytes);
 /* trajectory (phase 1 then phase 2) after lrs_solve: curr and oracle ranks */
 int lrs_trajectory(lrs_ctx *ctx, int phase, int *curr_rank, int *oracle_rank, int cap);
 /* JSON like lorads_logging.c:618-712 */

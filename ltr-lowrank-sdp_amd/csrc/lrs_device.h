@@ -365,6 +365,13 @@ constexpr int kGramMaxChunks = 64;
 size_t gram_buf_len(int rmax);
 int launch_gram(const DevProblem &P, int cone, const double *X, const double *Y, int avg,
                 double *gram, int *nblk_used, hipStream_t st, bool reduce = true);
+// Y = X Q on one cone's rows (k_rot): X (or (X + X2)/2, X2 non-null) n x ld
+// row-major with rp = 4 ceil(r / 4) <= ld columns read, Q row-major rp x rot_q_ld(ldn) (zero rows
+// past r, zero columns past k), Y n x ldn row-major, columns [k, ldn) written 0.  The pointers are
+// the cone's own rows (no cone offset is added).  rot_q_ld: Q's row pitch for an output pitch ldn.
+int rot_q_ld(int ldn);
+int launch_rot(int n, int r, int ld, int k, int ldn, const double *X, const double *X2, const double *Q,
+               double *Y, hipStream_t st);
 // sustained v_mfma_f64_16x16x4f64 rate: every CU, 2 waves a SIMD, 8 accumulators a wave
 int mfma_f64_peak(hipStream_t st, double *tflops);
 int mfma_f64_probe(hipStream_t st, int wps, int chains, double *tflops, double *mhz, double *cyc_per_mfma);

@@ -6552,6 +6552,97 @@ int launch_gram(const DevProblem &P, int cone, const double *X, const double *Y,
     return 0;
 }
 
+// k_rot: Y = X Q on one cone's rows, the rotation of a factor to the principal axes of its Gram
+// (DESIGN.md §4.15), on the FP64 matrix cores (v_mfma_f64_16x16x4f64; fragment map as k_gram's:
+// A[l & 15][l >> 4], B[l >> 4][l & 15], D col = l & 15, row = (l >> 4) + 4q).  A wave owns 16 rows
+// and NT output tiles of 16 columns (blockIdx.y picks the group of NT tiles, so wide outputs are
+// split over gridDim.y instead of spilling); per step of 4 columns c of X its lane reads one
+// double of row i0 + (l & 15) at column c + (l >> 4) (X, or (X + X2)/2 formed in registers as
+// gram_loop does) and NT doubles of Q's rows c + (l >> 4) straight from L2 (Q is rp x ldq, at most
+// 2 MB, read by every wave).  Every output element is ONE accumulator chain over c = 0, 4, 8, ...:
+// the bits do not depend on the grid.  Q carries zero rows in [r, rp) and zero columns from k on;
+// X's columns [r, ld) are the layout's zero padding and rp <= ld, so every read is inside the
+// row.  Rows >= n are clamped on load and not stored; columns [k, ldn) of Y are stored as 0 (every
+// row kernel relies on zero padding), columns >= ldn not at all.  No LDS, no atomics.
+template <int NT, bool AVG>
+__global__ void __launch_bounds__(kBlock) k_rot(int n, int rp, int ld, int k, int ldn, int ldq,
+                                                const double *__restrict__ X, const double *__restrict__ X2,
+                                                const double *__restrict__ Q, double *__restrict__ Y) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long i0 = ((long)blockIdx.x * (kBlock / 64) + w) * 16;
+    if (i0 >= n) return;   // wave-uniform
+    const int j0 = blockIdx.y * 16 * NT, m = lane & 15, kk = lane >> 4;
+    const long xo = min(i0 + m, (long)n - 1) * ld + kk;
+    const double *__restrict__ qb = Q + (long)kk * ldq + j0 + m;
+    gram_acc_t acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = gram_acc_t{0.0, 0.0, 0.0, 0.0};
+    int c = 0;
+    for (; c + 16 <= rp; c += 16) {   // four steps' loads in flight before their MFMAs
+        double a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            a[u] = X[xo + c + 4 * u];
+            if constexpr (AVG) a[u] = 0.5 * (a[u] + X2[xo + c + 4 * u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const double *__restrict__ qc = qb + (long)(c + 4 * u) * ldq;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], qc[16 * t], acc[t], 0, 0, 0);
+        }
+    }
+    for (; c < rp; c += 4) {
+        double a = X[xo + c];
+        if constexpr (AVG) a = 0.5 * (a + X2[xo + c]);
+        const double *__restrict__ qc = qb + (long)c * ldq;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, qc[16 * t], acc[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int col = j0 + 16 * t + m;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const long row = i0 + kk + 4 * q;
+            if (row < n && col < ldn) Y[row * ldn + col] = col < k ? acc[t][q] : 0.0;
+        }
+    }
+}
+// tiles a wave of k_rot: 4 where the output has at least four, so that a row of X is read once
+// per 64 output columns
+static int rot_nt(int ldn) {
+    const int tiles = (ldn + 15) / 16;
+    return tiles >= 4 ? 4 : tiles >= 2 ? 2 : 1;
+}
+int rot_q_ld(int ldn) {
+    const int nt = rot_nt(ldn), tiles = (ldn + 15) / 16;
+    return 16 * nt * ((tiles + nt - 1) / nt);
+}
+int launch_rot(int n, int r, int ld, int k, int ldn, const double *X, const double *X2, const double *Q,
+               double *Y, hipStream_t st) {
+    const int rp = (r + 3) / 4 * 4, nt = rot_nt(ldn), ldq = rot_q_ld(ldn);
+    if (n < 1 || r < 1 || k < 1 || k > ldn || rp > ld) {
+        snprintf(g_err, sizeof(g_err), "rot: n %d r %d ld %d k %d ldn %d", n, r, ld, k, ldn);
+        return -1;
+    }
+    const dim3 grid((n + 16 * (kBlock / 64) - 1) / (16 * (kBlock / 64)), ldq / (16 * nt));
+#define LRS_ROT_GO(NT_)                                                                                         \
+    do {                                                                                                        \
+        if (X2)                                                                                                 \
+            hipLaunchKernelGGL((k_rot<NT_, true>), grid, dim3(kBlock), 0, st, n, rp, ld, k, ldn, ldq, X, X2, Q, Y); \
+        else                                                                                                    \
+            hipLaunchKernelGGL((k_rot<NT_, false>), grid, dim3(kBlock), 0, st, n, rp, ld, k, ldn, ldq, X, X2, Q, Y); \
+    } while (0)
+    if (nt == 4) LRS_ROT_GO(4);
+    else if (nt == 2) LRS_ROT_GO(2);
+    else LRS_ROT_GO(1);
+#undef LRS_ROT_GO
+    LRS_CHECK_LAUNCH();
+    return 0;
+}
+
 // Row-kernel grids of the split iteration, sized from the occupancy query: a stage
 // launches min(rows' lane groups, blocks resident on the whole chip).  When one
 // resident wave of groups covers every row (latency regime, small n) the neighbour

@@ -149,6 +149,11 @@ struct lrs_ctx {
     long xwg_snap_len = 0;
     bool small_off = false;
     int xwg_fallbacks = 0;
+    // rank reduction: lrs_set_rank_shrink's rule (tol <= 0: off) and the last
+    // lrs_factor_compress's k_rot time (HIP events around its launches) and algorithmic bytes
+    double shrink_tol = 0.0;
+    int shrink_slack = 0;
+    double rot_ms = 0.0, rot_bytes = 0.0;
     // L-BFGS mirror
     int head = 0, gcur = 0;
     double beta[2] = {0, 0}, yy[2] = {0, 0};
@@ -664,9 +669,10 @@ static int zero_work(lrs_ctx *c, bool keep_point = false) {
     return 0;
 }
 
-static int alloc_work(lrs_ctx *c, const std::vector<int> &ranks) {
+static int alloc_work(lrs_ctx *c, const std::vector<int> &ranks, bool fresh = false) {
     // same ranks as the live workspace: keep the buffers (and the captured graphs), zero them
-    if (c->walloc && ranks == c->rank) return zero_work(c);
+    // (fresh, compress_impl: new buffers whatever the ranks -- the old factors were taken out)
+    if (!fresh && c->walloc && ranks == c->rank) return zero_work(c);
     free_work(c);
     DevProblem &P = c->dp;
     c->rank = ranks;
@@ -1395,6 +1401,130 @@ static int sym_count(int r, std::vector<double> A, double eps) {
     const double mx = 0.5 * (lo + hi);
     if (!(mx > 0)) return 0;
     return r - below(eps * mx);
+}
+
+// All eigenvalues (descending) and, with Zt, eigenvectors of the symmetric r x r matrix A
+// (lrs_sym_eig): sym_count's Householder reduction with the reflectors kept, Q =
+// H_0 H_1 ... accumulated backwards, then implicit QL with Wilkinson shifts on the tridiagonal, its
+// rotations applied to the vectors.  Zt holds the vectors as ROWS (row j the vector of w[j]: the
+// rotations touch two contiguous rows, and the buffer is lrs_sym_eig's column-major q as it
+// stands).  jacobi_eig is written for m <= 64; this is O(r^3) with a small constant at r = 512.
+// Sign: each vector's component of largest magnitude is positive (the first one on a tie).
+// Single-threaded and branch-deterministic: the same bits on every call.  Returns -1 when an
+// eigenvalue has not converged in 64 QL sweeps.
+static int sym_eig(int r, std::vector<double> A, double *wout, double *Zt) {
+    std::vector<double> d(r), e(r, 0.0), v(r), w(r), beta(r, 0.0);
+    // reflector k's vector is kept in column k below the diagonal (rows k + 1 .. r - 1)
+    for (int k = 0; k < r - 2; ++k) {
+        double alpha = 0.0;
+        for (int i = k + 1; i < r; ++i) alpha += A[i * r + k] * A[i * r + k];
+        alpha = std::sqrt(alpha);
+        if (alpha == 0.0) { e[k] = 0.0; continue; }
+        const double x0 = A[(k + 1) * r + k];
+        if (x0 > 0) alpha = -alpha;
+        double vn = 0.0;
+        for (int i = k + 1; i < r; ++i) v[i] = A[i * r + k];
+        v[k + 1] -= alpha;
+        for (int i = k + 1; i < r; ++i) vn += v[i] * v[i];
+        if (vn == 0.0) { e[k] = x0; continue; }
+        e[k] = alpha;
+        // A <- H A H on the trailing block, H = I - 2 v v^T / (v^T v)
+        const double bk = 2.0 / vn;
+        double vw = 0.0;
+        for (int i = k + 1; i < r; ++i) {
+            double t = 0.0;
+            for (int j = k + 1; j < r; ++j) t += A[i * r + j] * v[j];
+            w[i] = bk * t;
+            vw += v[i] * w[i];
+        }
+        const double hk = 0.5 * bk * vw;
+        for (int i = k + 1; i < r; ++i) w[i] -= hk * v[i];
+        for (int i = k + 1; i < r; ++i)
+            for (int j = k + 1; j < r; ++j) A[i * r + j] -= v[i] * w[j] + w[i] * v[j];
+        for (int i = k + 1; i < r; ++i) A[i * r + k] = v[i];
+        beta[k] = bk;
+    }
+    for (int i = 0; i < r; ++i) d[i] = A[i * r + i];
+    if (r >= 2) e[r - 2] = A[(r - 1) * r + (r - 2)];
+    if (Zt) {
+        // Zt = Q^T, Q = H_0 H_1 ... H_{r-3}: Q^T <- Q^T H_k for k descending touches rows and
+        // columns k + 1 .. r - 1 only (row j of Zt is column j of Q)
+        for (long i = 0; i < (long)r * r; ++i) Zt[i] = 0.0;
+        for (int i = 0; i < r; ++i) Zt[(long)i * r + i] = 1.0;
+        for (int k = r - 3; k >= 0; --k) {
+            if (beta[k] == 0.0) continue;
+            for (int j = k + 1; j < r; ++j) {   // row j <- row j - beta (row j . v) v^T
+                double t = 0.0;
+                double *zj = Zt + (long)j * r;
+                for (int i = k + 1; i < r; ++i) t += A[i * r + k] * zj[i];
+                t *= beta[k];
+                for (int i = k + 1; i < r; ++i) zj[i] -= t * A[i * r + k];
+            }
+        }
+    }
+    // implicit QL on tridiag(e, d, e); e[i] couples i and i + 1
+    const double eps = 2.220446049250313e-16;
+    for (int l = 0; l < r; ++l) {
+        int iter = 0, m;
+        do {
+            for (m = l; m < r - 1; ++m) {
+                const double dd = std::fabs(d[m]) + std::fabs(d[m + 1]);
+                if (std::fabs(e[m]) <= eps * dd) break;
+            }
+            if (m != l) {
+                if (iter++ == 64) return -1;
+                double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
+                double rr = std::hypot(g, 1.0);
+                g = d[m] - d[l] + e[l] / (g + (g >= 0 ? std::fabs(rr) : -std::fabs(rr)));
+                double s = 1.0, cc = 1.0, p = 0.0;
+                int i;
+                for (i = m - 1; i >= l; --i) {
+                    double f = s * e[i];
+                    const double b = cc * e[i];
+                    rr = std::hypot(f, g);
+                    e[i + 1] = rr;
+                    if (rr == 0.0) { d[i + 1] -= p; e[m] = 0.0; break; }
+                    s = f / rr;
+                    cc = g / rr;
+                    g = d[i + 1] - p;
+                    rr = (d[i] - g) * s + 2.0 * cc * b;
+                    p = s * rr;
+                    d[i + 1] = g + p;
+                    g = cc * rr - b;
+                    if (Zt) {
+                        double *z0 = Zt + (long)i * r, *z1 = Zt + (long)(i + 1) * r;
+                        for (int q = 0; q < r; ++q) {
+                            f = z1[q];
+                            z1[q] = s * z0[q] + cc * f;
+                            z0[q] = cc * z0[q] - s * f;
+                        }
+                    }
+                }
+                if (rr == 0.0 && i >= l) continue;
+                d[l] -= p;
+                e[l] = g;
+                e[m] = 0.0;
+            }
+        } while (m != l);
+    }
+    // descending order (stable: equal eigenvalues keep the iteration's order), then the sign rule
+    std::vector<int> ord(r);
+    for (int i = 0; i < r; ++i) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return d[a] > d[b]; });
+    for (int j = 0; j < r; ++j) wout[j] = d[ord[j]];
+    if (Zt) {
+        std::vector<double> T((size_t)r * r);
+        for (int j = 0; j < r; ++j) {
+            const double *z = Zt + (long)ord[j] * r;
+            int big = 0;
+            for (int i = 1; i < r; ++i)
+                if (std::fabs(z[i]) > std::fabs(z[big])) big = i;
+            const double sg = z[big] < 0 ? -1.0 : 1.0;
+            for (int i = 0; i < r; ++i) T[(size_t)j * r + i] = sg * z[i];
+        }
+        memcpy(Zt, T.data(), sizeof(double) * (size_t)r * r);
+    }
+    return 0;
 }
 
 static int gram_of(lrs_ctx *c, int k, const double *X, const double *Y, int avg, std::vector<double> &g) {
@@ -4214,6 +4344,133 @@ int lrs_certified_bound(lrs_ctx *c, double *bound, double *lam_min, int *converg
     return 0;
 }
 
+// ---- rank reduction: rotate the factors to the principal axes of their Gram
+struct ConeSpectrum {
+    std::vector<double> w;   // eigenvalues of the cone's r x r Gram, descending
+    std::vector<double> q;   // eigenvectors, column-major r x r (empty when not asked for)
+    int count = 0;           // eigenvalues > rel_tol * w[0]
+};
+// every cone's Gram of R (LRS_R) or of (U + V)/2 (LRS_U) on the device, its eigenvalues on the host
+static int factor_spectra(lrs_ctx *c, int which, double rel_tol, bool vectors, std::vector<ConeSpectrum> &sp) {
+    const int K = c->dp.K;
+    sp.assign(K, ConeSpectrum());
+    std::vector<double> g;
+    for (int k = 0; k < K; ++k) {
+        const int r = c->rank[k];
+        if (which == LRS_R) { if (gram_of(c, k, c->W.R, nullptr, 0, g)) return -1; }
+        else { if (gram_of(c, k, c->W.U, c->W.V, 1, g)) return -1; }
+        sp[k].w.resize(r);
+        if (vectors) sp[k].q.resize((size_t)r * r);
+        if (sym_eig(r, g, sp[k].w.data(), vectors ? sp[k].q.data() : nullptr)) {
+            set_err("cone %d: the eigen-solver of the %d x %d Gram did not converge", k, r, r);
+            return -1;
+        }
+        for (int j = 0; j < r; ++j) sp[k].count += sp[k].w[j] > rel_tol * sp[k].w[0] ? 1 : 0;
+    }
+    return 0;
+}
+static int spectrum_rank(const ConeSpectrum &s, int r, int slack) { return std::min(r, std::max(1, s.count + slack)); }
+
+// lrs_factor_compress after its refusals.  new_ranks (may be null): a cone's entry > 0 wins over
+// the rule.  only_if_lower (the in-solve hook): nothing is touched unless some cone's rank drops;
+// *did says whether the workspace was rebuilt.  The old R, U, V and LAMBDA allocations are taken
+// out of the workspace before alloc_work frees and rebuilds it, k_rot runs old -> new, then they
+// are freed: the factors never visit the host (its traffic is the Grams down and Q up).
+static int compress_impl(lrs_ctx *c, int which, const int *new_ranks, double rel_tol, int slack, bool only_if_lower,
+                         int *ranks_out, double *eigs, double *lost, double *qout, bool *did) {
+    const int K = c->dp.K;
+    std::vector<ConeSpectrum> sp;
+    if (factor_spectra(c, which, rel_tol, true, sp)) return -1;
+    std::vector<int> nr(K);
+    bool lower = false;
+    for (int k = 0; k < K; ++k) {
+        const int r = c->rank[k];
+        if (is_lp(c, k)) nr[k] = 1;
+        else if (new_ranks && new_ranks[k] > 0) nr[k] = new_ranks[k];
+        else nr[k] = spectrum_rank(sp[k], r, slack);
+        lower = lower || nr[k] < r;
+    }
+    if (did) *did = lower || !only_if_lower;
+    if (only_if_lower && !lower) return 0;
+    // the old geometry, and Q per cone padded for k_rot: rows to a multiple of 4, columns to the
+    // kernel's pitch, zeros outside [0, r) x [0, k)
+    struct Old { int n, r, ld; long foff, qoff; };
+    std::vector<Old> old(K);
+    long qlen = 0;
+    for (int k = 0; k < K; ++k) {
+        const DevCone &dc = c->dp.cones[k];
+        old[k] = Old{dc.n, dc.r, dc.ld, dc.foff, qlen};
+        qlen += (long)((dc.r + 3) / 4 * 4) * rot_q_ld(choose_layout(nr[k]).ld);
+    }
+    std::vector<double> hq(qlen, 0.0);
+    long eo = 0, qo = 0;
+    double bytes = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const int r = old[k].r, ldq = rot_q_ld(choose_layout(nr[k]).ld);
+        for (int j = 0; j < nr[k]; ++j)
+            for (int i = 0; i < r; ++i) hq[old[k].qoff + (long)i * ldq + j] = sp[k].q[(size_t)j * r + i];
+        if (ranks_out) ranks_out[k] = nr[k];
+        if (eigs) std::copy(sp[k].w.begin(), sp[k].w.end(), eigs + eo);
+        if (qout) std::copy(sp[k].q.begin(), sp[k].q.end(), qout + qo);
+        if (lost) {
+            double s = 0.0;
+            for (int j = nr[k]; j < r; ++j) s += std::max(sp[k].w[j], 0.0);
+            lost[k] = s;
+        }
+        eo += r;
+        qo += (long)r * r;
+        bytes += 8.0 * old[k].n * ((which == LRS_R ? 1.0 : 2.0) * r + nr[k]);
+    }
+    double *dQ = nullptr;
+    HIPC(hipMalloc((void **)&dQ, sizeof(double) * qlen));
+    if (h2d_sync(c, dQ, hq.data(), sizeof(double) * qlen) != hipSuccess) {
+        (void)hipFree(dQ);
+        set_err("lrs_factor_compress: upload of the rotations failed");
+        return -1;
+    }
+    DevWork &W = c->W;
+    double *oR = W.R, *oU = W.U, *oV = W.V, *oLam = W.lam;
+    W.R = W.U = W.V = W.lam = nullptr;
+    auto drop_old = [&]() {
+        for (double *p : {oR, oU, oV, oLam, dQ})
+            if (p) (void)hipFree(p);
+    };
+    if (alloc_work(c, nr, true)) { drop_old(); return -1; }
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int rc = 0;
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) rc = -1;
+    if (!rc) (void)hipEventRecord(ev[0], c->st);
+    for (int k = 0; k < K && !rc; ++k) {
+        const DevCone &dc = c->dp.cones[k];
+        const Old &o = old[k];
+        if (is_lp(c, k) && which == LRS_R) {   // rank 1 before and after: the same layout, the same bits
+            if (hipMemcpyAsync(W.R + dc.foff, oR + o.foff, sizeof(double) * o.n * o.ld, hipMemcpyDeviceToDevice,
+                               c->st) != hipSuccess)
+                rc = -1;
+            continue;
+        }
+        const double *X = (which == LRS_R ? oR : oU) + o.foff;
+        if (launch_rot(o.n, o.r, o.ld, nr[k], dc.ld, X, which == LRS_R ? nullptr : oV + o.foff, dQ + o.qoff,
+                       W.R + dc.foff, c->st))
+            rc = -1;
+    }
+    if (!rc) (void)hipEventRecord(ev[1], c->st);
+    const size_t fb = sizeof(double) * c->dp.NRpad;
+    if (!rc && (hipMemcpyAsync(W.U, W.R, fb, hipMemcpyDeviceToDevice, c->st) != hipSuccess ||
+                hipMemcpyAsync(W.V, W.R, fb, hipMemcpyDeviceToDevice, c->st) != hipSuccess ||
+                hipMemcpyAsync(W.lam, oLam, sizeof(double) * std::max(1, c->dp.m), hipMemcpyDeviceToDevice, c->st) !=
+                    hipSuccess))
+        rc = -1;
+    if (hipStreamSynchronize(c->st) != hipSuccess) rc = -1;
+    float ms = 0.0f;
+    if (!rc && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) { c->rot_ms = ms; c->rot_bytes = bytes; }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    drop_old();
+    if (rc) { set_err("lrs_factor_compress: the rotation failed on the device: %s", last_device_error()); return -1; }
+    return 0;
+}
+
 static int warm_reset(lrs_ctx *c, const lrs_params *p);
 static int solve_impl(lrs_ctx *c, const lrs_params *pin, lrs_result *res, bool warm = false) {
     lrs_params prm = *pin;
@@ -4277,6 +4534,16 @@ static int solve_impl(lrs_ctx *c, const lrs_params *pin, lrs_result *res, bool w
     double dinf = -1.0;   // not evaluated (phase 2 skipped)
     int dinf_conv = -1;
     if (!timeout && !p->skipADMM) {
+        // lrs_set_rank_shrink: the ALM point rotated to its principal axes and cut to the rule's
+        // ranks, once, when that lowers some cone's rank (batch members keep their ranks)
+        if (c->shrink_tol > 0 && !sharded(c) && !c->batch) {
+            const int before = sum_rank(c);
+            bool did = false;
+            if (compress_impl(c, LRS_R, nullptr, c->shrink_tol, c->shrink_slack, true, nullptr, nullptr, nullptr,
+                              nullptr, &did))
+                return -1;
+            if (did) logf_(c, p, "rank shrink: %d -> %d\n", before, sum_rank(c));
+        }
         if (alm_to_admm(c, p, alm, admm)) return -1;
         const double ta = now_s();
         int arc = admm_optimize(c, p, admm, p->maxADMMIter, tss);
@@ -4423,6 +4690,77 @@ int lrs_solve_warm(lrs_ctx *c, const lrs_params *p, lrs_result *res) {
         return -6;
     }
     return solve_impl(c, p, res, true);
+}
+
+// ---- rank reduction (no reference counterpart)
+int lrs_sym_eig(int r, const double *a, double *w, double *q) {
+    if (r < 1 || !a || !w) { set_err("lrs_sym_eig: r = %d (>= 1), a and w non-null", r); return -2; }
+    // the mean of the two triangles: what a symmetric matrix is, whatever rounding left in them
+    std::vector<double> A((size_t)r * r);
+    for (int i = 0; i < r; ++i)
+        for (int j = 0; j < r; ++j) A[(size_t)i * r + j] = 0.5 * (a[(size_t)i * r + j] + a[(size_t)j * r + i]);
+    if (sym_eig(r, std::move(A), w, q)) { set_err("lrs_sym_eig: no convergence in 64 QL sweeps"); return -1; }
+    return 0;
+}
+
+// the refusals lrs_factor_spectrum and lrs_factor_compress share
+static int compress_refuse(lrs_ctx *c, const char *who, int which, double rel_tol) {
+    if (sharded(c)) { set_err("%s: sharded contexts are not supported", who); return -3; }
+    if (!c->walloc || c->rank.size() != (size_t)c->dp.K) { set_err("%s: no solver state (ranks not set)", who); return -6; }
+    if (which != LRS_R && which != LRS_U) { set_err("%s: selector %d (LRS_R or LRS_U)", who, which); return -11; }
+    if (!(rel_tol >= 0.0 && rel_tol < 1.0)) { set_err("%s: rel_tol %g outside [0, 1)", who, rel_tol); return -2; }
+    return 0;
+}
+
+int lrs_factor_spectrum(lrs_ctx *c, int which, double rel_tol, double *eigs, int *counts) {
+    LRS_NEED_LOADED(c);
+    if (int rc = compress_refuse(c, "lrs_factor_spectrum", which, rel_tol)) return rc;
+    std::vector<ConeSpectrum> sp;
+    if (factor_spectra(c, which, rel_tol, false, sp)) return -1;
+    long eo = 0;
+    for (int k = 0; k < c->dp.K; ++k) {
+        if (eigs) std::copy(sp[k].w.begin(), sp[k].w.end(), eigs + eo);
+        if (counts) counts[k] = sp[k].count;
+        eo += c->rank[k];
+    }
+    return 0;
+}
+
+int lrs_factor_compress(lrs_ctx *c, int which, const int *new_ranks, double rel_tol, int slack, int *ranks_out,
+                        double *eigs, double *lost, double *q) {
+    LRS_NEED_LOADED(c);
+    if (int rc = compress_refuse(c, "lrs_factor_compress", which, rel_tol)) return rc;
+    if (slack < 0) { set_err("lrs_factor_compress: slack %d < 0", slack); return -2; }
+    for (int k = 0; new_ranks && k < c->dp.K; ++k) {
+        if (is_lp(c, k)) {
+            if (new_ranks[k] != 0 && new_ranks[k] != 1) {
+                set_err("lrs_factor_compress: the LP cone (cone %d) stays at rank 1, got %d", k, new_ranks[k]);
+                return -2;
+            }
+        } else if (new_ranks[k] < 0 || new_ranks[k] > c->rank[k]) {
+            set_err("lrs_factor_compress: cone %d: rank %d outside 0 .. %d (0: the rule)", k, new_ranks[k], c->rank[k]);
+            return -2;
+        }
+    }
+    return compress_impl(c, which, new_ranks, rel_tol, slack, false, ranks_out, eigs, lost, q, nullptr);
+}
+
+int lrs_set_rank_shrink(lrs_ctx *c, double rel_tol, int slack) {
+    LRS_NEED_CTX(c);
+    if (!(rel_tol < 1.0) || slack < 0) {
+        set_err("lrs_set_rank_shrink: rel_tol %g (< 1; <= 0: off), slack %d (>= 0)", rel_tol, slack);
+        return -2;
+    }
+    c->shrink_tol = rel_tol > 0 ? rel_tol : 0.0;
+    c->shrink_slack = slack;
+    return 0;
+}
+
+int lrs_compress_timing(lrs_ctx *c, double *rot_ms, double *rot_bytes) {
+    LRS_NEED_CTX(c);
+    if (rot_ms) *rot_ms = c->rot_ms;
+    if (rot_bytes) *rot_bytes = c->rot_bytes;
+    return 0;
 }
 
 // ---- batched solves

@@ -19,6 +19,13 @@
 // above `--triangleMinViol v` (default 0); `--triangleFile PATH` receives them, `i j k type
 // violation` a line (i < j < k 1-based, type 0..3, %.17g); the JSON gains a "triangles" object.  A
 // cone that does not qualify gets one line on stderr and nothing else.
+// `--compressTol t` (with `--compressSlack s`, default 0) after the last solve rotates the final
+// point to the principal axes of its Gram and keeps the eigenvalues above t times the largest, plus
+// s (lrs_factor_compress; the source is (U + V) / 2 if the ADMM phase ran, else R);
+// the JSON gains a "compressed" object {"ranks", "lost_trace", "spectrum"}.  With --cutRounds the
+// loop also compresses R before every warm re-solve.  `--rankShrink t` turns the in-solve hook on
+// (lrs_set_rank_shrink(t, s)): the ADMM phase runs at the ranks the ALM point needs.  --batch
+// ignores the three.
 #include <getopt.h>
 
 #include <cctype>
@@ -81,6 +88,8 @@ struct Flags {
     int cutRounds = 0;
     bool cutDrop = false;
     double cutDropSlack = 0.0;
+    double compressTol = -1.0, rankShrink = 0.0;   // < 0 / <= 0: off
+    int compressSlack = 0;
 };
 static void parse_flags(int argc, char **argv, Flags &F) {
     lrs_params &p = F.p;
@@ -106,7 +115,8 @@ static void parse_flags(int argc, char **argv, Flags &F) {
         {"roundLocalSearch", required_argument, 0, 2008}, {"roundFile", required_argument, 0, 2009},
         {"triangleCuts", required_argument, 0, 2010}, {"triangleMinViol", required_argument, 0, 2011},
         {"triangleFile", required_argument, 0, 2012}, {"cutRounds", required_argument, 0, 2013},
-        {"cutDropSlack", required_argument, 0, 2014}, {0, 0, 0, 0}};
+        {"cutDropSlack", required_argument, 0, 2014}, {"compressTol", required_argument, 0, 2015},
+        {"compressSlack", required_argument, 0, 2016}, {"rankShrink", required_argument, 0, 2017}, {0, 0, 0, 0}};
     int opt, li = 0;
     optind = 0;   // a fresh scan (one per manifest line)
     while ((opt = getopt_long(argc, argv, "r:", opts, &li)) != -1) {
@@ -153,6 +163,9 @@ static void parse_flags(int argc, char **argv, Flags &F) {
         case 2012: F.triangleFile = optarg; break;
         case 2013: F.cutRounds = atoi(optarg); break;
         case 2014: F.cutDrop = true; F.cutDropSlack = atof(optarg); break;
+        case 2015: F.compressTol = atof(optarg); break;
+        case 2016: F.compressSlack = atoi(optarg); break;
+        case 2017: F.rankShrink = atof(optarg); break;
         default: break;   // unknown flags: getopt already printed a message; ignored like main.c
         }
     }
@@ -409,7 +422,10 @@ static void cut_rounds(lrs_ctx *ctx, const Flags &F, lrs_result &r, std::string 
             if (lrs_cuts_drop(ctx, mark.data(), 1, &dropped)) break;
         }
         lrs_result rr;
-        if (lrs_cuts_append(ctx, fresh.data(), (int)(fresh.size() / 4), 1, &added) || lrs_solve_warm(ctx, &F.p, &rr)) {
+        if (lrs_cuts_append(ctx, fresh.data(), (int)(fresh.size() / 4), 1, &added) ||
+            (F.compressTol >= 0 && lrs_factor_compress(ctx, LRS_R, nullptr, F.compressTol, F.compressSlack, nullptr, nullptr,
+                                                       nullptr, nullptr)) ||
+            lrs_solve_warm(ctx, &F.p, &rr)) {
             fprintf(stderr, "[lrsdp] cut round %d failed: %s\n", rnd + 1, lrs_last_error());
             break;
         }
@@ -435,6 +451,48 @@ static void cut_rounds(lrs_ctx *ctx, const Flags &F, lrs_result &r, std::string 
 }
 
 // --batch FILE: load every line's instance, one lrs_solve_batch, one JSON each
+// --compressTol t after the last solve: the final point compressed in the context, and the JSON at
+// jsonFile (if any) gains "compressed" before its closing brace
+static void compress_and_report(lrs_ctx *ctx, const Flags &F, const lrs_result &r, const char *jsonFile) {
+    if (F.compressTol < 0) return;
+    int m = 0, K = 0;
+    lrs_problem_info(ctx, &m, &K, nullptr, nullptr, nullptr);
+    std::vector<int> old(K > 0 ? K : 1, 0), nr(old);
+    lrs_get_rank(ctx, old.data());
+    size_t tot = 0;
+    for (int k = 0; k < K; ++k) tot += (size_t)old[k];
+    std::vector<double> eigs(tot ? tot : 1, 0.0), lost(old.size(), 0.0);
+    const int which = (r.admm_iter > 0 || r.traj2_len > 0) ? LRS_U : LRS_R;
+    if (lrs_factor_compress(ctx, which, nullptr, F.compressTol, F.compressSlack, nr.data(), eigs.data(), lost.data(),
+                            nullptr)) {
+        fprintf(stderr, "[lrsdp] compression skipped: %s\n", lrs_last_error());
+        return;
+    }
+    auto num = [](double v) {
+        char b[40];
+        snprintf(b, sizeof(b), "%.16e", v);
+        return std::string(b);
+    };
+    std::string ranks, lt, sp;
+    size_t off = 0;
+    int before = 0, after = 0;
+    for (int k = 0; k < K; ++k) {
+        ranks += (k ? ", " : "") + std::to_string(nr[k]);
+        lt += (k ? ", " : "") + num(lost[k]);
+        sp += k ? ", [" : "[";
+        for (int j = 0; j < old[k]; ++j) sp += (j ? ", " : "") + num(eigs[off + j]);
+        sp += "]";
+        off += (size_t)old[k];
+        before += old[k];
+        after += nr[k];
+    }
+    printf("Compression (%s, tol %g, slack %d): rank %d -> %d\n", which == LRS_U ? "(U+V)/2" : "R", F.compressTol,
+           F.compressSlack, before, after);
+    if (jsonFile)
+        json_append(jsonFile, ",\n  \"compressed\": {\"ranks\": [" + ranks + "], \"lost_trace\": [" + lt +
+                                  "], \"spectrum\": [" + sp + "]}\n}\n");
+}
+
 static int run_batch(const Flags &base, const char *prog) {
     FILE *f = fopen(base.batchFile.c_str(), "r");
     if (!f) {
@@ -600,6 +658,8 @@ int main(int argc, char **argv) {
     lrs_problem_info(ctx, &m, &K, nullptr, nullptr, nullptr);
     printf("Reading SDPA file in %f seconds \n", tread);
     printf("nConstrs = %d, sdp nBlks = %d, lp Cols = %d\n", m, K, 0);
+    if (F.rankShrink > 0 && lrs_set_rank_shrink(ctx, F.rankShrink, F.compressSlack))
+        fprintf(stderr, "[lrsdp] --rankShrink ignored: %s\n", lrs_last_error());
     lrs_result r;
     if (lrs_solve(ctx, &p, &r)) {
         fprintf(stderr, "[lrsdp] solve failed: %s\n", lrs_last_error());
@@ -642,6 +702,7 @@ int main(int argc, char **argv) {
     // after cut rounds the triangles' report is the rounds' (the file holds the final cut list)
     if (rounds.empty()) triangles_and_report(ctx, F, jsonFile);
     else if (jsonFile) json_append(jsonFile, ",\n  \"cut_rounds\": [" + rounds + "\n  ]\n}\n");
+    compress_and_report(ctx, F, r, jsonFile);
     lrs_ctx_destroy(ctx);
     return 0;
 }

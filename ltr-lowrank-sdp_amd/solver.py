@@ -176,6 +176,11 @@ def load_library(path=None):
         "lrs_cuts_get": (C.c_int, [vp, ip, C.c_int, ip]),
         "lrs_cuts_state": (C.c_int, [vp, C.c_int, dp, dp]),
         "lrs_certified_bound": (C.c_int, [vp, dp, dp, ip]),
+        "lrs_sym_eig": (C.c_int, [C.c_int, dp, dp, dp]),
+        "lrs_factor_spectrum": (C.c_int, [vp, C.c_int, C.c_double, dp, ip]),
+        "lrs_factor_compress": (C.c_int, [vp, C.c_int, ip, C.c_double, C.c_int, ip, dp, dp, dp]),
+        "lrs_set_rank_shrink": (C.c_int, [vp, C.c_double, C.c_int]),
+        "lrs_compress_timing": (C.c_int, [vp, dp, dp]),
         "lrs_shard_plan": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_long), ip, ip, ip, ip, ip, ip, ip]),
     }
     for name, (res, args) in sig.items():
@@ -247,6 +252,31 @@ class CutError(RuntimeError):
         super().__init__(f"{what} ({code}): {msg}")
         self.code = code
         self.message = msg
+
+
+class CompressError(RuntimeError):
+    """A refused Solver.spectrum / compress / set_rank_shrink or sym_eig: `code` is the library's
+    negative return value."""
+
+    def __init__(self, what, code, msg):
+        super().__init__(f"{what} ({code}): {msg}")
+        self.code = code
+        self.message = msg
+
+
+def sym_eig(a, vectors=True):
+    """Eigenvalues (descending) and eigenvectors of a symmetric matrix on the host (lrs_sym_eig:
+    Householder tridiagonalisation, implicit QL): (w, q) with q[:, j] the unit eigenvector of w[j],
+    its component of largest magnitude positive; vectors=False returns w alone."""
+    lib = load_library()
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    r = a.shape[0] if a.ndim == 2 and a.shape[0] == a.shape[1] else 0
+    w = np.empty(max(1, r))
+    q = np.empty((max(1, r), max(1, r))) if vectors else None
+    rc = lib.lrs_sym_eig(r, _dptr(a), _dptr(w), _dptr(q) if vectors else None)
+    if rc != 0:
+        raise CompressError("sym_eig", rc, lib.lrs_last_error().decode())
+    return (w, np.ascontiguousarray(q.T)) if vectors else w   # q is column-major in the library
 
 
 def round_dirs(seed, r, trials):
@@ -653,14 +683,79 @@ class Solver:
                         "certified_bound")
         return b.value, lm.value, bool(cv.value)
 
-    def cut_loop(self, rounds, max_cuts, min_violation=1e-6, drop_slack=None, round_trials=0, **solve_kw):
+    # ---- rank reduction (include/lrsdp.h lrs_factor_spectrum .. lrs_set_rank_shrink)
+    def _compress_check(self, rc, what):
+        if rc != 0:
+            raise CompressError(what, rc, self.lib.lrs_last_error().decode())
+
+    def spectrum(self, which=R, rel_tol=1e-6):
+        """(eigs, counts): per cone the eigenvalues of the Gram of factor `which` (R, or U for the
+        phase-2 point (U + V) / 2), descending, and how many exceed rel_tol times the largest.
+        Changes nothing.  A refusal raises CompressError."""
+        ranks = self.get_rank() if self.ctx else []
+        tot = max(1, sum(ranks)) if len(ranks) == self.K else 1
+        e = np.zeros(tot)
+        cnt = (C.c_int * max(1, self.K))()
+        self._compress_check(self.lib.lrs_factor_spectrum(self.ctx, which, float(rel_tol), _dptr(e), cnt), "spectrum")
+        offs = np.concatenate([[0], np.cumsum(ranks)]).astype(int)
+        return [e[offs[k]:offs[k + 1]].copy() for k in range(self.K)], list(cnt)[:self.K]
+
+    def compress(self, ranks=None, rel_tol=1e-6, slack=0, which=R, return_q=False):
+        """Rotate factor `which` (R, or U for (U + V) / 2) to the principal axes of its Gram on the
+        device and keep the leading columns: per SDP cone ranks[k] when given and > 0, else min(r,
+        max(1, count(rel_tol) + slack)).  Afterwards R = U = V = the compressed point at the new
+        ranks, LAMBDA kept, everything else as after set_rank.  Returns {"ranks", "eigs" (a list per
+        cone, at the old ranks), "lost" (trace dropped per cone)} and, with return_q, "q" (per cone
+        the r x r eigenvector matrix, new R = old R @ q[:, :k]).  A refusal raises CompressError."""
+        old = self.get_rank() if self.ctx else []
+        ok = len(old) == self.K and all(r > 0 for r in old)
+        tot = max(1, sum(old)) if ok else 1
+        tq = max(1, sum(r * r for r in old)) if ok else 1
+        e, lost = np.zeros(tot), np.zeros(max(1, self.K))
+        qb = np.zeros(tq) if return_q else None
+        out = (C.c_int * max(1, self.K))()
+        nr = None
+        if ranks is not None:
+            ranks = [int(v) for v in ranks]
+            if len(ranks) != self.K:
+                raise ValueError(f"compress: {len(ranks)} ranks for {self.K} cones")
+            nr = (C.c_int * max(1, self.K))(*ranks)
+        rc = self.lib.lrs_factor_compress(self.ctx, which, nr, float(rel_tol), int(slack), out, _dptr(e), _dptr(lost),
+                                          _dptr(qb) if return_q else None)
+        self._compress_check(rc, "compress")
+        self._refresh_info()
+        offs = np.concatenate([[0], np.cumsum(old)]).astype(int)
+        res = {"ranks": list(out)[:self.K], "eigs": [e[offs[k]:offs[k + 1]].copy() for k in range(self.K)],
+               "lost": lost[:self.K].tolist()}
+        if return_q:
+            qo = np.concatenate([[0], np.cumsum([r * r for r in old])]).astype(int)
+            res["q"] = [np.ascontiguousarray(qb[qo[k]:qo[k + 1]].reshape(old[k], old[k]).T) for k in range(self.K)]
+        return res
+
+    def set_rank_shrink(self, rel_tol, slack=0):
+        """solve() / solve_warm() compress the ALM point once before the ADMM phase when the rule
+        min(r, max(1, count(rel_tol) + slack)) lowers some cone's rank; rel_tol <= 0 turns it off
+        (the default).  Batched solves ignore it."""
+        self._compress_check(self.lib.lrs_set_rank_shrink(self.ctx, float(rel_tol), int(slack)), "set_rank_shrink")
+
+    def compress_timing(self):
+        """(ms, bytes) of the last compress()'s rotation kernel launches: HIP events, algorithmic bytes."""
+        ms, by = C.c_double(), C.c_double()
+        self._check(self.lib.lrs_compress_timing(self.ctx, C.byref(ms), C.byref(by)), "compress_timing")
+        return ms.value, by.value
+
+    def cut_loop(self, rounds, max_cuts, min_violation=1e-6, drop_slack=None, round_trials=0, compress_tol=None,
+                 compress_slack=0, **solve_kw):
         """Cutting-plane rounds in this context: round 0 is the plain solve(); each later round
         separates max_cuts + E inequalities at R (E: registered cuts violated by more than
         min_violation), takes the max_cuts most violated that are not registered yet, stops when
         none is new, optionally drops cuts with slack > drop_slack and lambda >= 0, appends with
         carry and calls solve_warm().  Returns one dict a round: n_cuts, n_added, n_dropped,
         n_violated, max_violation, pobj, dobj, certified_bound, bound_converged, alm_inner,
-        admm_iter, time_sec, and best_value when round_trials > 0."""
+        admm_iter, time_sec, and best_value when round_trials > 0.  compress_tol (None: off):
+        compress(rel_tol=compress_tol, slack=compress_slack) on R before each solve_warm(), so a
+        warm round runs at the rank its start needs; each round's dict then carries `rank`, the SDP
+        cone's rank at the end of the round."""
         import time as _time
         out = []
 
@@ -672,6 +767,8 @@ class Solver:
                    "alm_inner": res["alm_inner"], "admm_iter": res["admm_iter"]}
             if round_trials > 0:
                 rec["best_value"] = self.round_signs(int(round_trials))["best_value"]
+            if compress_tol is not None:
+                rec["rank"] = int(self.get_rank()[0])
             rec["time_sec"] = _time.perf_counter() - t0
             out.append(rec)
 
@@ -694,6 +791,8 @@ class Solver:
             if drop_slack is not None and have.shape[0]:
                 nd = self.drop_cuts((slack > drop_slack) & (lam >= 0.0), carry=True)
             na = self.append_cuts(np.asarray(new, dtype=np.int32), carry=True)
+            if compress_tol is not None:
+                self.compress(rel_tol=compress_tol, slack=compress_slack)
             res = self.solve_warm(**solve_kw)
             record(res, t0, na, nd, nv, mv)
         return out
