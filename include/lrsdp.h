@@ -28,7 +28,10 @@
  * lrs_op_alm_update, lrs_op_adjoint, lrs_op_auv and lrs_op_dimacs added.
  * 3: lrs_solve_warm, lrs_cuts_append / _drop / _get / _state and lrs_certified_bound added.
  * 4: lrs_sym_eig, lrs_factor_spectrum, lrs_factor_compress, lrs_set_rank_shrink and
- * lrs_compress_timing added (lrs_params and lrs_result unchanged). */
+ * lrs_compress_timing added (lrs_params and lrs_result unchanged).
+ * Read-only diagnostic getters (lrs_get_kernel_path, lrs_lat_plain_used, lrs_lat_tsum_used,
+ * lrs_get_layout, lrs_factor_padding, ...) are additive and leave the revision as it is: it moves
+ * when a signature or a struct changes or a family of operations is added. */
 #define LRSDP_ABI_VERSION 4
 #ifdef __cplusplus
 extern "C" {
@@ -492,6 +495,16 @@ int lrs_lat_plain_used(lrs_ctx *ctx, int *used);
  * wave sums as transposed butterflies (wave_tsum: the same pair tree as one wave sum a value, so
  * the same bits), else 0.  The environment variable LRS_LAT_TSUM=0 selects one wave sum a value. */
 int lrs_lat_tsum_used(lrs_ctx *ctx, int *used);
+/* The lane layout of `cone`'s factor rows at the context's current ranks (after lrs_set_rank or a
+ * solve): every factor array of the cone is row-major n x ld on the device, a row held by G lanes
+ * with E doubles each, ld = G E >= the cone's rank, the columns [rank, ld) zero.  G, E and ld may
+ * each be NULL.  Diagnostics and tests (which template instantiation of the kernels a rank runs;
+ * the environment variable LRS_LAYOUT=GxE forces one wherever it holds the rank). */
+int lrs_get_layout(lrs_ctx *ctx, int cone, int *G, int *E, int *ld);
+/* *max_abs = the largest |x| over the padding columns [rank, ld) of every row of factor `which`
+ * (LRS_R .. LRS_Y1) in every cone, read back from the device as it is stored; a NaN counts as
+ * infinite.  Every kernel reduces over whole padded rows, so this is 0 at all times (tests). */
+int lrs_factor_padding(lrs_ctx *ctx, int which, double *max_abs);
 
 /* Standalone A(UU^T) on R (the constraint-entry kernel k_auv_con, all cones): reps
  * launches back to back between two HIP events, average ms per launch; and its

@@ -680,8 +680,10 @@ static int alloc_work(lrs_ctx *c, const std::vector<int> &ranks, bool fresh = fa
     long off = 0;
     int rmax = 1;
     for (int k = 0; k < P.K; ++k) {
+        // past the widest layout choose_layout finds none and leaves ld at its 2^30 sentinel, which
+        // would size every factor array: refused here (every rank up to kMaxRankLd has a layout)
+        if (ranks[k] > kMaxRankLd) { set_err("rank %d unsupported (max %d)", ranks[k], kMaxRankLd); return -1; }
         Layout L = choose_layout(ranks[k]);
-        if (ranks[k] > L.ld) { set_err("rank %d unsupported (max 512)", ranks[k]); return -1; }
         c->lay[k] = L;
         DevCone &dc = P.cones[k];
         dc.r = ranks[k]; dc.ld = L.ld; dc.G = L.G; dc.E = L.E; dc.foff = off;
@@ -3192,6 +3194,37 @@ int lrs_lat_tsum_used(lrs_ctx *c, int *used) {
     LRS_NEED_CTX(c);
     LRS_NEED_ARG(used);
     *used = (c->loaded && c->dp.last_path == 0) ? c->dp.last_tsum : 0;
+    return 0;
+}
+
+int lrs_get_layout(lrs_ctx *c, int cone, int *G, int *E, int *ld) {
+    LRS_NEED_STATE(c);
+    if (cone < 0 || cone >= c->dp.K) { set_err("lrs_get_layout: cone %d of %d", cone, c->dp.K); return -1; }
+    const Layout &L = c->lay[cone];
+    if (G) *G = L.G;
+    if (E) *E = L.E;
+    if (ld) *ld = L.ld;
+    return 0;
+}
+
+int lrs_factor_padding(lrs_ctx *c, int which, double *max_abs) {
+    LRS_NEED_STATE(c);
+    LRS_NEED_ARG(max_abs);
+    const double *d = factor_ptr(c, which);
+    if (!d) { set_err("bad factor id"); return -1; }
+    std::vector<double> h(c->dp.NRpad);
+    HIPC(hipStreamSynchronize(c->st));
+    HIPC(hipMemcpy(h.data(), d, sizeof(double) * c->dp.NRpad, hipMemcpyDeviceToHost));
+    double mx = 0.0;
+    for (int k = 0; k < c->dp.K; ++k) {
+        const DevCone &dc = c->dp.cones[k];
+        for (int i = 0; i < dc.n; ++i)
+            for (int q = dc.r; q < dc.ld; ++q) {
+                const double v = std::fabs(h[dc.foff + (long)i * dc.ld + q]);
+                if (!(v <= mx)) mx = (v == v) ? v : HUGE_VAL;   // a NaN counts as infinite
+            }
+    }
+    *max_abs = mx;
     return 0;
 }
 

@@ -124,6 +124,8 @@ def load_library(path=None):
         "lrs_get_kernel_path": (C.c_int, [vp, ip]),
         "lrs_lat_plain_used": (C.c_int, [vp, ip]),
         "lrs_lat_tsum_used": (C.c_int, [vp, ip]),
+        "lrs_get_layout": (C.c_int, [vp, C.c_int, ip, ip, ip]),
+        "lrs_factor_padding": (C.c_int, [vp, C.c_int, dp]),
         "lrs_wave_tsum_probe": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp]),
         "lrs_stage_bytes": (C.c_int, [vp, dp]),
         "lrs_tile_info": (C.c_int, [vp, ip, ip]),
@@ -951,6 +953,20 @@ class Solver:
         v = C.c_int(0)
         self._check(self.lib.lrs_lat_tsum_used(self.ctx, C.byref(v)), "lat_tsum_used")
         return bool(v.value)
+
+    def layout(self, cone=0):
+        """(G, E, ld) of `cone`'s factor rows at the current ranks: G lanes a row, E doubles a lane,
+        ld = G E >= rank the row pitch on the device (lrs_get_layout)."""
+        g, e, ld = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.lib.lrs_get_layout(self.ctx, int(cone), C.byref(g), C.byref(e), C.byref(ld)), "get_layout")
+        return g.value, e.value, ld.value
+
+    def factor_padding(self, which=R):
+        """The largest |x| in the padding columns [rank, ld) of factor `which` as stored on the device
+        (lrs_factor_padding); 0 unless a kernel wrote past the rank."""
+        v = C.c_double()
+        self._check(self.lib.lrs_factor_padding(self.ctx, int(which), C.byref(v)), "factor_padding")
+        return v.value
 
     def wave_tsum_probe(self, form, x):
         """The latency kernels' wave sums of x in both forms, (ref, new), each [nv]

@@ -40,6 +40,13 @@ CASES = [
     ("checker_1.5", os.path.join(ROOT, "data", "bundled", "checker_1.5.dat-s"), -1, [1, 3, 5]),
     # rank 290 > 256 (the 64 x 8 layout): the n x r arrays stored as n x 4 projections R @ Omega
     ("mc_rand300w_r290", os.path.join(GOLD, "instances", "mc_rand300w.dat-s"), 290, [1, 2, 3, 5, 8]),
+    # the upper edges of the 16 x 3, 64 x 3 and 64 x 4 layouts and the lower edge of 64 x 2 (no other
+    # fixture reaches those layouts; tests/test_gpu_layouts.py sweeps them against the oracle, which
+    # these pin to the reference there): projections as above
+    ("mc_rand300w_r48", os.path.join(GOLD, "instances", "mc_rand300w.dat-s"), 48, [1, 2, 3, 5, 8]),
+    ("mc_rand300w_r97", os.path.join(GOLD, "instances", "mc_rand300w.dat-s"), 97, [1, 2, 3, 5, 8]),
+    ("mc_rand300w_r192", os.path.join(GOLD, "instances", "mc_rand300w.dat-s"), 192, [1, 2, 3, 5, 8]),
+    ("mc_rand300w_r256", os.path.join(GOLD, "instances", "mc_rand300w.dat-s"), 256, [1, 2, 3, 5, 8]),
     # dense objective (C5b structure at test size, the reference's dense branches): the instance is
     # regenerated from ltr-lowrank-sdp_amd/instances.py random_sparse(300, 3000, 6, 7, dense_c=True)
     ("rdense300", "gen:rdense300", -1, [1, 2, 3, 4, 5]),
@@ -53,7 +60,8 @@ CASES = [
 ]
 FLAGS = {"mc_rand200_l3": ["--lbfgsListLength", "3"], "theta40_l3": ["--lbfgsListLength", "3"]}
 GEN = {"rdense300": (300, 3000, 6, 7)}
-PROJ = {"mc_rand300w_r290": 4}
+PROJ = {"mc_rand300w_r290": 4, "mc_rand300w_r48": 4, "mc_rand300w_r97": 4, "mc_rand300w_r192": 4,
+        "mc_rand300w_r256": 4}
 
 
 def project(v, n, k, seed=7):

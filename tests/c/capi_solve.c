@@ -74,6 +74,8 @@ static int null_contract(void) {
     EXPECT_FAIL(lrs_set_log_path(NULL, "x.log"));
     EXPECT_FAIL(lrs_set_kernel_path(NULL, 0));
     EXPECT_FAIL(lrs_get_kernel_path(NULL, &iv));
+    EXPECT_FAIL(lrs_get_layout(NULL, 0, &iv, &iv, &iv));
+    EXPECT_FAIL(lrs_factor_padding(NULL, LRS_R, &dv));
     EXPECT_FAIL(lrs_time_auut(NULL, 1, &dv));
     EXPECT_FAIL(lrs_auut_bytes(NULL, &dv));
     EXPECT_FAIL(lrs_time_gram(NULL, 0, 1, &dv, NULL));

@@ -26,9 +26,11 @@ from golden_util import GOLDEN, ROOT, rel_err
 
 pytestmark = pytest.mark.gpu
 STEP_CASES = ["mc_rand200", "mc_torus12x10", "mc_rand300w", "theta40", "theta25x3", "rsparse60", "checker_1.5",
-              "mc_rand300w_r290", "mc_lp60"]
-# fixtures whose n x r arrays are stored as n x k projections V @ Omega (scripts/make_golden_steps.py)
-PROJ = {"mc_rand300w_r290": 4}
+              "mc_rand300w_r290", "mc_lp60", "mc_rand300w_r48", "mc_rand300w_r97", "mc_rand300w_r192",
+              "mc_rand300w_r256"]
+# fixtures whose n x r arrays are stored as n x k projections V @ Omega (scripts/make_golden_steps.py);
+# r48 ... r256: the reference itself at the 16 x 3, 64 x 2, 64 x 3 and 64 x 4 layouts
+PROJ = {f"mc_rand300w_r{r}": 4 for r in (290, 48, 97, 192, 256)}
 
 
 def project(v, n, k, seed=7):

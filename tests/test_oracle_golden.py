@@ -54,8 +54,11 @@ def test_oracle_solve_matches_reference(oracle_lib, case):
 
 
 STEP_CASES = ["mc_rand200", "mc_torus12x10", "mc_rand300w", "theta40", "theta25x3", "rsparse60", "checker_1.5",
-              "mc_rand300w_r290", "mc_lp60"]
-PROJ = {"mc_rand300w_r290": 4}   # n x r arrays stored as n x 4 projections (make_golden_steps.py)
+              "mc_rand300w_r290", "mc_lp60", "mc_rand300w_r48", "mc_rand300w_r97", "mc_rand300w_r192",
+              "mc_rand300w_r256"]
+# n x r arrays stored as n x 4 projections (make_golden_steps.py); r48 ... r256: the 16 x 3, 64 x 2,
+# 64 x 3 and 64 x 4 layouts, where tests/test_gpu_layouts.py takes the restatement as its reference
+PROJ = {f"mc_rand300w_r{r}": 4 for r in (290, 48, 97, 192, 256)}
 
 
 def _proj(v, n, k, seed=7):
