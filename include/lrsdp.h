@@ -501,6 +501,15 @@ int lrs_lat_tsum_used(lrs_ctx *ctx, int *used);
  * each be NULL.  Diagnostics and tests (which template instantiation of the kernels a rank runs;
  * the environment variable LRS_LAYOUT=GxE forces one wherever it holds the rank). */
 int lrs_get_layout(lrs_ctx *ctx, int cone, int *G, int *E, int *ld);
+/* The LP block's ADMM column sweep as the next launch will run it (read-only; every pointer may be
+ * NULL).  *lp_cone = the LP block's cone, -1 without one (the other outputs are then 0).  *staged =
+ * 1 when the sweep's operands fit the LDS limit (152 KB, lowered by the environment variable
+ * LRS_LP_LDS_MAX in bytes, read per launch; 0 forces the other variant) and the walk reads them
+ * there, 0 when it walks global memory.  *lds_bytes = what the staged variant needs for this
+ * problem, *entries = the LP block's constraint entries on the device, *dense_dropped = the
+ * constraint entries of its columns present in >= m/4 constraints, which the reference's column
+ * typing drops (their squared norm stays in the update's denominator).  Diagnostics and tests. */
+int lrs_lp_sweep_info(lrs_ctx *ctx, int *lp_cone, int *staged, long *lds_bytes, long *entries, long *dense_dropped);
 /* *max_abs = the largest |x| over the padding columns [rank, ld) of every row of factor `which`
  * (LRS_R .. LRS_Y1) in every cone, read back from the device as it is stored; a NaN counts as
  * infinite.  Every kernel reduces over whole padded rows, so this is 0 at all times (tests). */

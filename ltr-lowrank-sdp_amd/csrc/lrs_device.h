@@ -96,6 +96,9 @@ struct DevCone {
     // the column's squared 2-norm (lp_cone_presolve nrm2Square, lorads_lp_conic.c:132-133)
     int *lp_slot = nullptr;
     double *lp_nrm2 = nullptr;
+    // LP cone: its entries' range [lp_e0, lp_e0 + lp_ne) of the slot CSR (upload_problem; the
+    // sweep's launch takes it from here), and the entries its LP_COEFF_DENSE columns lost
+    long lp_e0 = 0, lp_ne = 0, lp_dense_dropped = 0;
     // rows the kernels compute: [row0, row0 + nown) -- the whole cone, or in a sharded
     // solve this process's rows (the others, the halo, are read as neighbours only)
     int row0 = 0, nown = 0;
@@ -509,6 +512,9 @@ int launch_small_eval(const DevProblem &P, DevWork &W, const double *U, const do
 // the LP block's ADMM update: the reference's closed-form column sweep (k_lp_admm), both sides
 int launch_lp_admm(const DevProblem &P, DevWork &W, double rho, hipStream_t st);
 long lp_sweep_scratch(const DevProblem &P);
+// which variant the next launch takes (1 operands staged in LDS, 0 the global-memory walk) under
+// the current LRS_LP_LDS_MAX, and the LDS bytes the staged variant needs for this problem
+void lp_sweep_plan(const DevProblem &P, int *staged, long *lds_bytes);
 int launch_small_cg_batch(const DevProblem &P, DevWork &W, int side, double rho, double tol, int maxit,
                           hipStream_t st);
 

@@ -9703,23 +9703,36 @@ long lp_sweep_scratch(const DevProblem &P) {   // doubles of W.lpw the unstaged 
     const DevCone &c = P.cones[P.lp_cone];
     return 2L * c.n + (c.P + 2) / 2 + 1;
 }
+// the staged limit: kLpMaxDynLds, lowered by LRS_LP_LDS_MAX (bytes, clamped to [0, kLpMaxDynLds];
+// 0 = the global-memory variant always), read per launch (tests)
+static size_t lp_sweep_cap() {
+    size_t cap = kLpMaxDynLds;
+    if (const char *e = getenv("LRS_LP_LDS_MAX")) {
+        const long long v = atoll(e);
+        cap = v <= 0 ? 0 : (size_t)std::min<long long>(v, (long long)kLpMaxDynLds);
+    }
+    return cap;
+}
+void lp_sweep_plan(const DevProblem &P, int *staged, long *lds_bytes) {
+    *staged = 0;
+    *lds_bytes = 0;
+    if (P.lp_cone < 0) return;
+    const DevCone &c = P.cones[P.lp_cone];
+    const size_t lds = lp_sweep_lds(P.m, c.n, c.P, c.lp_ne);
+    *lds_bytes = (long)lds;
+    *staged = lds <= lp_sweep_cap() ? 1 : 0;
+}
 int launch_lp_admm(const DevProblem &P, DevWork &W, double rho, hipStream_t st) {
     if (P.lp_cone < 0) return 0;
     const DevCone &c = P.cones[P.lp_cone];
     LpSweepArgs A{};
     A.m = P.m; A.n = c.n; A.ld = c.ld; A.slot_off = c.slot_off; A.P = c.P; A.foff = c.foff;
-    std::vector<int> sp(2);
-    if (hipMemcpy(sp.data(), P.slot_ptr + c.slot_off, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(sp.data() + 1, P.slot_ptr + c.slot_off + c.P, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
-        snprintf(g_err, sizeof(g_err), "launch_lp_admm: slot range read failed");
-        return -1;
-    }
-    A.e0 = sp[0]; A.ne = sp[1] - sp[0];
+    A.e0 = c.lp_e0; A.ne = c.lp_ne;
     A.lp_slot = c.lp_slot; A.slot_ptr = P.slot_ptr; A.slot_con = P.slot_con; A.slot_a = P.slot_a;
     A.lp_nrm2 = c.lp_nrm2; A.Craw = P.Craw; A.b = P.b; A.lam = W.lam;
     A.U = W.U; A.V = W.V; A.cvs = W.cvs; A.cvc = W.cvc + (long)P.lp_cone * P.m; A.rho = rho;
     const size_t lds = lp_sweep_lds(P.m, c.n, c.P, A.ne);
-    if (lds <= kLpMaxDynLds) {
+    if (lds <= lp_sweep_cap()) {
         static bool attr = false;
         if (!attr) {
             if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_lp_admm<true>),

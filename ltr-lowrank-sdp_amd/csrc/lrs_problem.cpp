@@ -1508,6 +1508,9 @@ bool upload_problem(const HostProblem &hp, DevProblem &dp, std::string &err) {
             std::vector<double> nr(c.lp_nrm2);
             if (nr.empty()) nr.push_back(0.0);
             if (!dput(&d.lp_slot, ls, err) || !dput(&d.lp_nrm2, nr, err)) return false;
+            d.lp_e0 = slot_ptr[d.slot_off];
+            d.lp_ne = slot_ptr[d.slot_off + d.P] - d.lp_e0;
+            d.lp_dense_dropped = c.lp_dense_dropped;
         }
         if (c.dense_c) {
             if (c.const_c) {

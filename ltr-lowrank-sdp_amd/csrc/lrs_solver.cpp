@@ -3207,6 +3207,20 @@ int lrs_get_layout(lrs_ctx *c, int cone, int *G, int *E, int *ld) {
     return 0;
 }
 
+int lrs_lp_sweep_info(lrs_ctx *c, int *lp_cone, int *staged, long *lds_bytes, long *entries, long *dense_dropped) {
+    LRS_NEED_LOADED(c);
+    int st = 0;
+    long lds = 0;
+    lp_sweep_plan(c->dp, &st, &lds);
+    const int k = c->dp.lp_cone;
+    if (lp_cone) *lp_cone = k;
+    if (staged) *staged = st;
+    if (lds_bytes) *lds_bytes = lds;
+    if (entries) *entries = k >= 0 ? c->dp.cones[k].lp_ne : 0;
+    if (dense_dropped) *dense_dropped = k >= 0 ? c->dp.cones[k].lp_dense_dropped : 0;
+    return 0;
+}
+
 int lrs_factor_padding(lrs_ctx *c, int which, double *max_abs) {
     LRS_NEED_STATE(c);
     LRS_NEED_ARG(max_abs);

@@ -18,6 +18,7 @@ import json
 import os
 import subprocess
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -125,6 +126,7 @@ def load_library(path=None):
         "lrs_lat_plain_used": (C.c_int, [vp, ip]),
         "lrs_lat_tsum_used": (C.c_int, [vp, ip]),
         "lrs_get_layout": (C.c_int, [vp, C.c_int, ip, ip, ip]),
+        "lrs_lp_sweep_info": (C.c_int, [vp, ip, ip, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
         "lrs_factor_padding": (C.c_int, [vp, C.c_int, dp]),
         "lrs_wave_tsum_probe": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp]),
         "lrs_stage_bytes": (C.c_int, [vp, dp]),
@@ -960,6 +962,18 @@ class Solver:
         g, e, ld = C.c_int(), C.c_int(), C.c_int()
         self._check(self.lib.lrs_get_layout(self.ctx, int(cone), C.byref(g), C.byref(e), C.byref(ld)), "get_layout")
         return g.value, e.value, ld.value
+
+    def lp_sweep_info(self):
+        """The LP block's ADMM column sweep as the next launch runs it (lrs_lp_sweep_info): lp_cone
+        (-1 without an LP block), staged (1 operands in LDS, 0 the global-memory walk, under the
+        current LRS_LP_LDS_MAX), lds_bytes the staged variant needs, entries on the device, and
+        dense_dropped (entries of columns in >= m/4 constraints, which the column typing drops)."""
+        k, st = C.c_int(), C.c_int()
+        lds, ne, dd = C.c_long(), C.c_long(), C.c_long()
+        self._check(self.lib.lrs_lp_sweep_info(self.ctx, C.byref(k), C.byref(st), C.byref(lds), C.byref(ne),
+                                               C.byref(dd)), "lp_sweep_info")
+        return SimpleNamespace(lp_cone=k.value, staged=st.value, lds_bytes=lds.value, entries=ne.value,
+                               dense_dropped=dd.value)
 
     def factor_padding(self, which=R):
         """The largest |x| in the padding columns [rank, ld) of factor `which` as stored on the device

@@ -75,6 +75,7 @@ static int null_contract(void) {
     EXPECT_FAIL(lrs_set_kernel_path(NULL, 0));
     EXPECT_FAIL(lrs_get_kernel_path(NULL, &iv));
     EXPECT_FAIL(lrs_get_layout(NULL, 0, &iv, &iv, &iv));
+    EXPECT_FAIL(lrs_lp_sweep_info(NULL, &iv, &iv, &lv, &lv, &lv));
     EXPECT_FAIL(lrs_factor_padding(NULL, LRS_R, &dv));
     EXPECT_FAIL(lrs_time_auut(NULL, 1, &dv));
     EXPECT_FAIL(lrs_auut_bytes(NULL, &dv));

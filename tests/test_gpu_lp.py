@@ -9,7 +9,9 @@ scripts/make_golden_steps.py):
   tests/golden/solves_lp.json           whole solves of mc_lp60 and of the reference's bundled shmup4
 
 Bars (per assertion): the sweep's U, V, lambda within 1e-6 (the SDP cone's CG at cg_tol 1e-9,
-as tests/test_gpu_small_cg.py) and the LP block's values alone within 1e-6; whole mc_lp60 solve
+as tests/test_gpu_small_cg.py) and the LP block's values alone within 1e-9 (closed-form arithmetic
+on sums that carry the CG's error; the sweep alone is pinned at rounding level in
+tests/test_gpu_lp_sweep.py); whole mc_lp60 solve
 reproduced step for step like the MaxCut solves (ALM inner +-2, objectives 1e-6, ADMM +-1);
 shmup4 (thousands of L-BFGS steps through 3 cones: trajectories diverge under FP64 summation
 order) within 10x the two certified gaps of the reference's objective, pinf <= 1e-4, same final
@@ -81,7 +83,7 @@ def test_lp_sweep_matches_reference(solver_mod):
         assert rel_err(ours, g[key]) < 1e-6, (key, rel_err(ours, g[key]))
     for key, ours in (("U", U), ("V", V)):
         e = rel_err(ours[nsdp:], g[key][nsdp:])
-        assert e < 1e-6, (key, "LP block", e)
+        assert e < 1e-9, (key, "LP block", e)
     sv.close()
 
 

@@ -156,7 +156,7 @@ def test_oracle_lp_sweep_matches_reference(oracle_lib):
         assert rel_err(ours, g[key]) < 1e-6, (key, rel_err(ours, g[key]))
     nsdp = dims[0] * rank
     for key, ours in (("U", U), ("V", V)):
-        assert rel_err(ours[nsdp:], g[key][nsdp:]) < 1e-6, (key, "LP block")
+        assert rel_err(ours[nsdp:], g[key][nsdp:]) < 1e-9, (key, "LP block", rel_err(ours[nsdp:], g[key][nsdp:]))
     assert abs(out[-1] - float(g["cg_total"])) <= max(4, 0.15 * float(g["cg_total"]))
 
 
